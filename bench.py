@@ -10,14 +10,22 @@ A step = one groupBy query over the rank's 8 segments: per-segment grouping + th
 GroupByMergingQueryRunnerV2 merge by value, i.e. the merged, ordered groups, produced in HBM
 (dg_groupby_run; LZ4 blocks decoded again every step, as the reference decompresses per query).
 The groups are not copied to the host inside the timed region (the boundary hands them over as a
-dg_result; the PCIe-inclusive rate is measured after the loop and reported as `pcie_fetch`).
+dg_result; with --full the PCIe-inclusive rate is measured after the loop and reported as `pcie_fetch`).
 For N > 1 (weak scaling, one process per GPU) the ranks' groups are exchanged by key range over RCCL
 and merged on the receiving GPU (dg_merge), so every rank ends with its range of the final result.
 
 The other configs (--config) are secondary lines / parity shapes: topn (configs[1]), timeseries
 (configs[0]), filtered (configs[3], one GPU's share), ts_hourly / groupby_hourly (configs[4]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config groupby|topn|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config groupby|topn|...] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: it writes (once) and attaches the
+segments, warms up, times the K steps and prints the result line (value, ms_per_step, the row and byte
+counts of the timed steps). --dump-outputs DIR also writes what the last timed step returned as
+DIR/<name>.npy (dump_outputs; the inputs are seeded, so two builds compare output for output). --full
+adds everything else, after the timed steps: the phase times and the roofline (untimed steps with
+phase timestamps), the PCIe-inclusive fetch, the CPU baseline and the result checks against it, the
+N-rank result checks and the device probes.
 
 --gpus N > 1 starts N ranks itself (launch_ranks) unless a launcher already did (WORLD_SIZE set,
 which must equal N); LOCAL_RANK picks the GPU (DG_BENCH_DEVICE overrides it for a one-GPU rehearsal).
@@ -736,6 +744,69 @@ def device_probes(NAT, device, line):
     return out
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: the most a dump holds (a larger groupBy result is sampled)
+DUMP_CHUNK = 16384     # groups per sampled run of consecutive groups
+DUMP_SEED = 9999
+
+
+def _hash48(v):
+    """A dimension value as a number a float64 holds exactly: the first 48 bits of the SHA-1 of its
+    UTF-8 bytes (null: -1)."""
+    import hashlib
+    return -1.0 if v is None else float(int.from_bytes(hashlib.sha1(v.encode("utf-8")).digest()[:6], "big"))
+
+
+def dump_sample(n, per_group_bytes):
+    """The groups of an n-group result that --dump-outputs writes, as (start, count) runs in ascending
+    order: all of them when they fit DUMP_BYTES, else seeded (DUMP_SEED) runs of DUMP_CHUNK consecutive
+    groups, the same for every result of n groups."""
+    if n * per_group_bytes <= DUMP_BYTES:
+        return [(0, n)] if n else []
+    runs = DUMP_BYTES // (per_group_bytes * DUMP_CHUNK)
+    picks = np.random.default_rng(DUMP_SEED).choice(n // DUMP_CHUNK, size=runs, replace=False)
+    return [(int(p) * DUMP_CHUNK, DUMP_CHUNK) for p in np.sort(picks)]
+
+
+def dump_outputs(out_dir, query, result, rank, world):
+    """--dump-outputs: what the last timed step returned, as out_dir/<name>.npy in float64 (N ranks:
+    rank<r>_<name>.npy, every rank its own part). A groupBy step leaves a dg_result in HBM: its group
+    count (`groups`) and, per group of dump_sample's runs (`group_index`), the bucket time, each
+    dimension's merged dictionary id and each aggregator's value (long sums are exact in float64 up
+    to 2^53). A timeseries / topN step returns the final rows: their timestamps, a topN row's dimension
+    value as _hash48, and each aggregator's value, in result order."""
+    Q = importlib.import_module("incubator-druid_amd.query")
+    arrays = {}
+    names = [a.name for a in query.aggregations]
+    if isinstance(query, Q.GroupByQuery):
+        nd = len(query.dimensions)
+        if result._dicts is None:  # (fetch() attaches the dictionaries to every partial: read them once)
+            result._dicts = [result.dictionary(d) for d in range(nd)]
+        runs = dump_sample(result.groups, 8 * (2 + nd + len(names)))
+        parts = [result.fetch(s, c) for s, c in runs]
+        cat = lambda cols: np.concatenate([np.asarray(c, dtype=np.float64) for c in cols]) if cols else np.zeros(0)  # noqa: E731
+        arrays["groups"] = [result.groups]
+        arrays["group_index"] = cat([np.arange(s, s + c) for s, c in runs])
+        arrays["time"] = cat([p.times for p in parts])
+        for d, dim in enumerate(query.dimensions):
+            arrays[f"dim_{dim}_id"] = cat([p.codes[d] for p in parts])
+        for k, name in enumerate(names):
+            arrays[f"agg_{name}"] = cat([p.aggs[k] for p in parts])
+    elif rank == 0:  # (N ranks: the all-reduced timeseries is the same on every rank; rank 0 holds the folded topN)
+        rows = []
+        for r in result or []:
+            for v in (r.value if isinstance(r.value, list) else [r.value]):
+                rows.append((r.timestamp, v))
+        arrays["timestamp"] = [t for t, _ in rows]
+        if isinstance(query, Q.TopNQuery):
+            arrays[f"dim_{query.dimension}_hash48"] = [_hash48(v[query.dimension]) for _, v in rows]
+        for name in names:
+            arrays[f"agg_{name}"] = [v[name] for _, v in rows]
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -807,9 +878,19 @@ def main():
     ap.add_argument("--no-result-checks", action="store_true", help="N ranks: skip the CPU-engine result checks")
     ap.add_argument("--no-probes", action="store_true", help="skip the device copy / link / gather probes")
     ap.add_argument("--write-workers", type=int, default=8, help="processes writing the synthetic segments")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline figure: phase "
+                         "times and the roofline, the PCIe-inclusive fetch, the CPU baseline and the result checks "
+                         "against it, the device probes (--no-cpu-baseline, --no-result-checks and --no-probes drop "
+                         "single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of a groupBy result beyond 48 MiB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # before torch or the engine is imported
     world, rank, local_rank = rank_env(args)
@@ -850,7 +931,9 @@ def main():
         dist.all_gather_object(gathered, mine)
         ts_buckets = sorted({b for g in gathered for b in g})
 
-    def step(stats):
+    def step(stats, keep=False):
+        """One step. keep: a groupBy step hands back its dg_result (the caller releases it) instead of
+        the group count, so that --dump-outputs can read what the last timed step left in HBM."""
         if isinstance(query, Q.TopNQuery):
             if dist is None:
                 return R.run_topn(segs, query, stats)
@@ -868,6 +951,8 @@ def main():
             merged = gmerge.exchange(res)  # this rank's key range of the cluster-wide result, in HBM
             res.release()
             res = merged
+        if keep:
+            return res
         n = res.groups
         res.release()
         return n
@@ -889,8 +974,9 @@ def main():
         dist.barrier()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        result = step(stats)
+    last = args.steps - 1 if args.dump_outputs else -1  # the step whose result --dump-outputs keeps
+    for i in range(args.steps):
+        result = step(stats, keep=i == last)
     sync()
     if dist is not None:
         dist.barrier()
@@ -899,10 +985,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, query, result, rank, world)
+        if isinstance(query, Q.GroupByQuery):
+            result.release()
+    del result
 
     NAT.lib().dg_set_phase_timing(1)
     pstats = R.RunStats()
-    psteps = min(PHASE_STEPS, args.steps)
+    psteps = min(PHASE_STEPS, args.steps) if args.full else 0
     for _ in range(psteps):
         step(pstats)
     sync()
@@ -911,7 +1002,8 @@ def main():
     calls = [c for c in stats.calls if c["segment_rows"] > 0]
     pcalls = [c for c in pstats.calls if c["segment_rows"] > 0]
     # counts and bytes from the timed steps; phase times (GPU timestamps) from the untimed phase steps
-    per_step = lambda k: (sum(c[k] for c in pcalls) / psteps if k.endswith("_ms") and k != "total_ms"  # noqa: E731
+    # (--full; a plain run takes none and reports no phase, roofline or per-kernel figure)
+    per_step = lambda k: (sum(c[k] for c in pcalls) / max(psteps, 1) if k.endswith("_ms") and k != "total_ms"  # noqa: E731
                           else sum(c[k] for c in calls) / steps)
     selected_local = per_step("selected_rows")
     scanned_local = sum(s.num_rows for s in segs)
@@ -948,7 +1040,7 @@ def main():
                                   max(per_step("lz4_general_launches"), 1.0), per_step("lz4_general_ms"))
     # LZ4 blocks per step by decoder (and those whose decode was fused with their aggregator)
     lz4_blocks = {"general": per_step("lz4_general_blocks"), "fused": per_step("lz4_fused_blocks")}
-    if isinstance(query, Q.GroupByQuery):
+    if args.full and isinstance(query, Q.GroupByQuery):
         phases.update({"keygen": per_step("keygen_ms"), "sort": per_step("sort_ms"), "reduce": per_step("reduce_ms"),
                        "reduce_kernels": per_step("reduce_kernel_ms")})
         passes = max(1, int(round(per_step("sort_passes"))))
@@ -1051,8 +1143,13 @@ def main():
                               "and aggregates every metric input")
     if isinstance(query, Q.GroupByQuery):
         line["groups_per_step"] = per_step("groups")
-    part = dicts = None
-    if isinstance(query, Q.GroupByQuery) and dist is None:
+    line["full"] = args.full
+    if not args.full:
+        # a plain run: the headline figure alone, no step beyond the timed ones
+        for k in ("roofline", "phases_ms", "phases_source", "topn_index"):
+            line.pop(k, None)
+    part = dicts = pool = None
+    if args.full and isinstance(query, Q.GroupByQuery) and dist is None:
         # the merged result, fetched to the host once (PCIe-inclusive; not part of `value`), and checked.
         # The destination is pinned host memory allocated once before the timing (the shim's direct
         # ByteBuffers, like the processing pool's startup allocation): the columns land by DMA.
@@ -1088,7 +1185,7 @@ def main():
                                  "double_sum": float(np.sum(part.aggs[1], dtype=np.float64)),
                                  "sorted": bool(gt.all())}
         del gt, eq
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the CPU baseline on the box's usable cores, and the result of the benched query checked
         # against it (or against the oracle) after the timed loop
         threads = _cpu_threads()
@@ -1112,7 +1209,7 @@ def main():
             cb, cres = cpu_baseline_topn(paths, query, threads)
             line["cpu_baseline"] = cb
             line["result_checks"] = check_topn(gpu_res, cres, query)
-    if dist is not None and not args.no_result_checks:
+    if args.full and dist is not None and not args.no_result_checks:
         # N ranks: the final result checked against every rank's CPU-engine result (after the timing; one
         # process per GPU, so the host cores are split between the node's ranks)
         threads = max(1, _cpu_threads() // int(os.environ.get("LOCAL_WORLD_SIZE", world)))
@@ -1154,9 +1251,9 @@ def main():
         if rank == 0 and "result_checks" in line:
             line["result_checks"]["check_s"] = time.perf_counter() - t_chk
     del part
-    if isinstance(query, Q.GroupByQuery) and dist is None:
+    if pool is not None:
         pool.close()
-    if rank == 0 and not args.no_probes:
+    if args.full and rank == 0 and not args.no_probes:
         line["device_probes"] = device_probes(NAT, device, line)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -25,7 +25,7 @@ def test_two_rank_bench_line_checks_its_answer(tmp_path, config):
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--config",
            config, "--rows", "200000", "--segments", "2", "--steps", "2", "--warmup", "1", "--data-dir",
-           str(tmp_path), "--no-cpu-baseline"]
+           str(tmp_path), "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -12,7 +12,7 @@ for round in 1 2; do
     # a variant is a library build (tools/build_variant.sh NAME) or env:VAR (the default library with VAR=1)
     envs=""; lib=""
     case "$v" in default) ;; env:*) envs="${v#env:}=1" ;; *) lib="$PWD/incubator-druid_amd/lib/variants/$v/libdruidgpu.so" ;; esac
-    env $envs DRUID_AMD_LIB=$lib timeout -k 10 300 python bench.py --config $CONFIG --steps $STEPS --warmup 2 --no-cpu-baseline \
+    env $envs DRUID_AMD_LIB=$lib timeout -k 10 300 python bench.py --full --config $CONFIG --steps $STEPS --warmup 2 --no-cpu-baseline \
       > gpurun_out/ab_${v#env:}.json 2> gpurun_out/ab_${v#env:}.err || { echo "variant $v failed"; tail -5 gpurun_out/ab_${v#env:}.err; exit 1; }
     python -c "
 import json,sys

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for cfg in ${CONFIGS:-topn_numeric topn_alphanumeric timeseries groupby filtered ts_hourly groupby_hourly}; do
   mode=${LZ4_MODE:-hc}  # the reference writes LZ4 blocks with lz4-java's high compressor
-  timeout -k 10 900 python -u bench.py --config "$cfg" --steps 5 --warmup 1 --cpu-seconds 8 --lz4-mode "$mode" \
+  timeout -k 10 900 python -u bench.py --full --config "$cfg" --steps 5 --warmup 1 --cpu-seconds 8 --lz4-mode "$mode" \
     > "gpurun_out/bench_$cfg.json" 2> "gpurun_out/bench_$cfg.err" || { echo "$cfg failed"; tail -5 "gpurun_out/bench_$cfg.err"; exit 4; }
   cut -c1-240 "gpurun_out/bench_$cfg.json"
 done

@@ -8,7 +8,7 @@ CONFIG=${CONFIG:-groupby}
 for round in 1 2; do
   for v in none ${VARIANTS:-}; do
     e=""; [ "$v" = none ] || e="${v//,/ }"
-    env $e timeout -k 10 600 python -u bench.py --config $CONFIG --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline \
+    env $e timeout -k 10 600 python -u bench.py --full --config $CONFIG --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline \
       > gpurun_out/envab_$round.json 2> gpurun_out/envab_$round.err || { tail -5 gpurun_out/envab_$round.err; exit 3; }
     python3 -c "
 import json; b=json.loads(open('gpurun_out/envab_$round.json').read().strip().splitlines()[-1])

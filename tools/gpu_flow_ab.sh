@@ -18,7 +18,7 @@ done
 for cfg in ${CONFIGS:-groupby ts_hourly}; do
   for v in flow noflow; do
     env=""; [ $v = noflow ] && env="DG_NO_FLOW_DECODE=1"
-    env $env timeout -k 10 600 python -u bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline \
+    env $env timeout -k 10 600 python -u bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline \
       > gpurun_out/${TAG}_bench_${cfg}_$v.json 2> gpurun_out/${TAG}_bench_${cfg}_$v.err || { tail -5 gpurun_out/${TAG}_bench_${cfg}_$v.err; exit 6; }
     python3 -c "
 import json; b=json.loads(open('gpurun_out/${TAG}_bench_${cfg}_$v.json').read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ for round in 1 2; do
   for cfg in ${CONFIGS:-ts_hourly}; do
     for v in default ${VARIANTS:-}; do
       lib=""; [ "$v" = default ] || lib="$PWD/incubator-druid_amd/lib/variants/$v/libdruidgpu.so"
-      DRUID_AMD_LIB=$lib timeout -k 10 600 python -u bench.py --config $cfg --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-probes \
+      DRUID_AMD_LIB=$lib timeout -k 10 600 python -u bench.py --full --config $cfg --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-probes \
         > gpurun_out/libab.json 2> gpurun_out/libab.err || { tail -5 gpurun_out/libab.err; exit 3; }
       python3 -c "
 import json; b=json.loads(open('gpurun_out/libab.json').read().strip().splitlines()[-1])

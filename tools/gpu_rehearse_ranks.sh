@@ -7,7 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for cfg in groupby timeseries topn; do
-  DG_DIST_BACKEND=gloo DG_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --gpus 2 --config $cfg --rows ${ROWS:-400000} --segments 2 \
+  DG_DIST_BACKEND=gloo DG_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --full --gpus 2 --config $cfg --rows ${ROWS:-400000} --segments 2 \
     --steps 3 --warmup 1 --data-dir /tmp/druid_amd_rehearse > gpurun_out/rehearse_$cfg.json 2> gpurun_out/rehearse_$cfg.err
   rc=$?
   echo "$cfg rc=$rc"; tail -c 400 gpurun_out/rehearse_$cfg.json; echo
