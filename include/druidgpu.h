@@ -25,6 +25,9 @@
  *   dg_groupby_run           <- GroupByStrategyV2.process -> GroupByQueryEngineV2.process per segment
  *                               (query/groupby/strategy/GroupByStrategyV2.java:472-477, epinephelinae/GroupByQueryEngineV2.java:91-187)
  *                               + GroupByStrategyV2.mergeRunners -> GroupByMergingQueryRunnerV2.run (:170-290)
+ *   dg_groupby_run_opts      <- the same under GroupByQueryConfig's forceHashAggregation / bufferGrouperMaxSize
+ *                               (query/groupby/GroupByQueryConfig.java:35-40): BufferHashGrouper over ByteBufferHashTable
+ *                               (epinephelinae/BufferHashGrouper.java:38-133, ByteBufferHashTable.java:286-327)
  *   dg_result_*              <- the merged grouper's sorted iterator (ConcurrentGrouper.iterator(true))
  *   dg_result_export / dg_keys_partition / dg_merge
  *                            <- QueryRunnerFactory.mergeRunners across devices (query/QueryRunnerFactory.java:62):
@@ -206,8 +209,9 @@ typedef struct {
   double total_ms;           /* whole call, host wall */
   /* groupBy phases (device time) and their element counts */
   double keygen_ms;          /* selected rows -> (key, row ref) */
-  double sort_ms;            /* radix passes */
-  double reduce_ms;          /* run heads + segmented reduce + floatSum pass + finalize */
+  double sort_ms;            /* radix passes (hash grouper: the table insert) */
+  double reduce_ms;          /* run heads + segmented reduce + floatSum pass + finalize (hash grouper: the group-count
+                                read-back, collect, group sort and emit) */
   int32_t sort_passes;
   int32_t key_bits;
   int64_t groups;            /* merged groups */
@@ -255,6 +259,12 @@ int dg_context_set_stream(dg_context* ctx, void* hip_stream);
  *   rows x the product of their value-list lengths, GroupByQueryEngineV2.java:480-540); never more
  *   than 2^32 - 64 (element indices are 32-bit). */
 #define DG_LIMIT_GROUP_ELEMENTS 1
+/*   DG_LIMIT_GROUPER: the grouper dg_groupby_run uses, a DG_GROUPER_* value (the context's
+ *   forceHashAggregation default, GroupByQueryConfig.java:35-40,179-200); <= 0: the sort.
+ *   DG_LIMIT_GROUPER_MAX_GROUPS: bufferGrouperMaxSize, the most groups one groupBy call may build; a
+ *   call that finds more fails with DG_ERR_TABLE_FULL; <= 0: unlimited. */
+#define DG_LIMIT_GROUPER 2
+#define DG_LIMIT_GROUPER_MAX_GROUPS 3
 int dg_context_set_limit(dg_context* ctx, int32_t which, int64_t value);
 
 /* ---- segments ---- */
@@ -377,6 +387,39 @@ typedef struct {
 
 int dg_groupby_run(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_groupby* g,
                    dg_result** out, dg_metrics* metrics);
+/* The grouper of one call (since ABI 16). DG_GROUPER_SORT: the call's elements sorted by key and
+ * reduced run by run. DG_GROUPER_HASH: BufferHashGrouper (epinephelinae/BufferHashGrouper.java:38-133)
+ * over an open-addressing table in HBM (ByteBufferHashTable.java:286-327: linear probing, max load factor
+ * 0.7), sized for max_groups, its groups sorted afterwards: the same result, a footprint and a sort
+ * sized by the groups. forceHashAggregation / bufferGrouperMaxSize of GroupByQueryConfig.java:35-40 map
+ * to `grouper` / `max_groups`. Like forceHashAggregation, `grouper` is a preference that never changes
+ * results: a plan with a floatSum aggregator (its fp32 row-order recurrence needs the sorted rows), a
+ * key of 64 bits or a table of more than 2^31 slots runs the sort (dg_result_grouper_info tells).
+ * max_groups: the table holds next_pow2(max_groups / 0.7) slots, max_groups capped at the call's
+ * elements and at 2^key_bits; a call that finds more distinct groups fails with DG_ERR_TABLE_FULL
+ * (Groupers.HASH_TABLE_FULL, there is no spilling), under either grouper, and leaves the context usable.
+ * dg_groupby_run(...) = dg_groupby_run_opts(..., NULL, ...). Environment DG_GROUPER=hash|sort overrides
+ * the context's default grouper per call (same-box A/B runs), never an explicit opts->grouper. */
+#define DG_GROUPER_SORT 0
+#define DG_GROUPER_HASH 1
+typedef struct {
+  int32_t grouper;      /* DG_GROUPER_*; -1 = the context's default */
+  int32_t reserved;
+  int64_t max_groups;   /* bufferGrouperMaxSize; <= 0 = the context's default (unlimited) */
+} dg_groupby_opts;
+int dg_groupby_run_opts(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_groupby* g,
+                        const dg_groupby_opts* opts /* NULL = defaults */, dg_result** out, dg_metrics* metrics);
+
+typedef struct {
+  int32_t grouper;          /* what actually ran */
+  int32_t reserved;
+  int64_t table_slots;      /* HBM table capacity (0 for the sort) */
+  int64_t max_groups;       /* the limit in force (0: none) */
+  int64_t flushed_entries;  /* LDS entries upserted into the HBM table */
+  int64_t direct_elements;  /* elements that bypassed a full LDS table */
+} dg_grouper_info;
+/* What grouped a dg_groupby_run result (a dg_merge result: the sort). */
+int dg_result_grouper_info(const dg_result* res, dg_grouper_info* out);
 /* ---- groupBy limit push-down ----
  * GroupByQuery.isApplyLimitPushDown (query/groupby/GroupByQuery.java:377-416: a limited DefaultLimitSpec
  * whose ORDER BY columns are all grouping dimensions, no having spec, no subtotals) orders rows by

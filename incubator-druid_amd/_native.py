@@ -24,6 +24,9 @@ COL_MISSING, COL_LONG, COL_FLOAT, COL_DOUBLE, COL_STRING, COL_UNSUPPORTED = rang
 F_AND, F_OR, F_NOT, F_SELECTOR, F_IN, F_BOUND = 1, 2, 3, 4, 5, 6
 ORDER = {"lexicographic": 0, "numeric": 1}
 LIMIT_GROUP_ELEMENTS = 1
+LIMIT_GROUPER, LIMIT_GROUPER_MAX_GROUPS = 2, 3
+GROUPER_SORT, GROUPER_HASH = 0, 1
+ERR_TABLE_FULL = 5
 
 
 class DruidGpuError(RuntimeError):
@@ -42,6 +45,11 @@ class QueryInterrupted(DruidGpuError):
 
 class ResourceLimitExceeded(DruidGpuError):
     pass
+
+
+class TableFull(ResourceLimitExceeded):
+    """DG_ERR_TABLE_FULL: more groups than bufferGrouperMaxSize (Groupers.HASH_TABLE_FULL; the shim
+    raises ResourceLimitExceededException)."""
 
 
 class dg_filter(ctypes.Structure):
@@ -99,6 +107,19 @@ class dg_groupby(ctypes.Structure):
     _fields_ = [("dimensions", ctypes.POINTER(ctypes.c_char_p)), ("n_dims", ctypes.c_int32)]
 
 
+class dg_groupby_opts(ctypes.Structure):
+    _fields_ = [("grouper", ctypes.c_int32), ("reserved", ctypes.c_int32), ("max_groups", ctypes.c_int64)]
+
+
+class dg_grouper_info(ctypes.Structure):
+    _fields_ = [("grouper", ctypes.c_int32), ("reserved", ctypes.c_int32), ("table_slots", ctypes.c_int64),
+                ("max_groups", ctypes.c_int64), ("flushed_entries", ctypes.c_int64),
+                ("direct_elements", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class dg_record_layout(ctypes.Structure):
     _fields_ = [("n_aggs", ctypes.c_int32), ("kinds", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("record_size", ctypes.c_int32), ("big_endian", ctypes.c_int32)]
@@ -137,6 +158,7 @@ EXPORTS = [
     "dg_merge", "dg_records_pack", "dg_debug_lz4_decode", "dg_result_limit",
     "dg_segment_from_rows", "dg_context_set_limit", "dg_groupby_merge_devices", "dg_timeseries_merge",
     "dg_debug_lz4_classify", "dg_host_alloc", "dg_host_free", "dg_set_phase_timing", "dg_debug_probe",
+    "dg_groupby_run_opts", "dg_result_grouper_info",
 ]
 
 _lib = None
@@ -187,6 +209,9 @@ def lib():
         "dg_topn_run": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_topn), vp, vp, vp, P(dg_metrics)]),
         "dg_topn_merge": (ctypes.c_int, [vp, P(dg_scan), P(dg_topn), P(dg_topn_lists), P(i32), vp, vp, vp]),
         "dg_groupby_run": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_groupby), P(vp), P(dg_metrics)]),
+        "dg_groupby_run_opts": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_groupby), P(dg_groupby_opts), P(vp),
+                                               P(dg_metrics)]),
+        "dg_result_grouper_info": (ctypes.c_int, [vp, P(dg_grouper_info)]),
         "dg_result_groups": (i64, [vp]),
         "dg_result_fetch_groups": (ctypes.c_int, [vp, i64, i64, vp, vp, vp]),
         "dg_result_fetch_rows": (ctypes.c_int, [vp, i64, i64, vp]),
@@ -226,7 +251,7 @@ def check(rc: int):
     if rc == 4:
         raise QueryInterrupted(rc, msg)
     if rc == 5:
-        raise ResourceLimitExceeded(rc, msg)
+        raise TableFull(rc, msg)
     raise DruidGpuError(rc, msg)
 
 

@@ -226,7 +226,7 @@ struct CallScratch {
   Pool host;
   UpPool up;
   // per-call device error word (bit 0: corrupt LZ4 block, bit 1: corrupt Roaring bitmap, bit 2:
-  // corrupt multi-value row lists), read once
+  // corrupt multi-value row lists, bit 3 = kErrTableFull: the hash grouper's table is full), read once
   // at the call's final synchronisation instead of after every kernel
   int32_t* d_err = nullptr;
   int32_t* h_err = nullptr;
@@ -402,6 +402,7 @@ static int finish_call(CallScratch* cs, hipStream_t st) {
   late.clear();
   DG_HIP(hipGetLastError());
   DG_HIP(take_launch_error());
+  if (cs->d_err && (*cs->h_err & kErrTableFull)) return set_error(DG_ERR_TABLE_FULL, "groupBy hash table full");
   if (cs->d_err && *cs->h_err)
     return set_error(DG_ERR_FORMAT, (*cs->h_err & 1)   ? "corrupt LZ4 block"
                                     : (*cs->h_err & 4) ? "corrupt multi-value row lists"
@@ -1955,6 +1956,13 @@ int dg_context_set_limit(dg_context* c, int32_t which, int64_t value) {
     case DG_LIMIT_GROUP_ELEMENTS:
       ctx->max_elements = value <= 0 ? ~0ull : (uint64_t)value;
       return DG_OK;
+    case DG_LIMIT_GROUPER:
+      if (value > DG_GROUPER_HASH) return set_error(DG_ERR_ARG, "unknown grouper %lld", (long long)value);
+      ctx->grouper = value <= 0 ? DG_GROUPER_SORT : (int32_t)value;
+      return DG_OK;
+    case DG_LIMIT_GROUPER_MAX_GROUPS:
+      ctx->max_groups = value <= 0 ? 0 : value;
+      return DG_OK;
     default: return set_error(DG_ERR_ARG, "unknown limit %d", which);
   }
 }
@@ -2279,12 +2287,14 @@ static bool has_float_sum(const AggPlan& plan) {
 }
 
 // device buffers of a sort-based grouping of at most `cap` rows with keys of key_bits bits (call
-// scratch): one 8-byte word per element [key | row ref] when both fit, else keys + a u32 ref array
-static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bits, int pw, SortBufs* sb) {
+// scratch): one 8-byte word per element [key | row ref] when both fit, else keys + a u32 ref array.
+// ref_bits >= 0: the references are not element indices but values of that many bits (hash table positions)
+static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bits, int pw, SortBufs* sb,
+                     int ref_bits = -1) {
   memset(sb, 0, sizeof *sb);
   sb->cap = cap;
   sb->ntiles_sort = sort_tiles(cap);
-  const int rb = bits_for(std::max<int64_t>(cap, 1));
+  const int rb = ref_bits >= 0 ? ref_bits : bits_for(std::max<int64_t>(cap, 1));
   const bool packed = key_bits + rb <= 64;
   sb->ref_bits = packed ? rb : 0;
   const size_t c = (size_t)std::max<int64_t>(cap, 1) + 16;
@@ -3834,6 +3844,7 @@ struct dg_result {
   std::vector<int32_t> cards;                         // dg_merge result: cluster dictionary sizes
   bool limited = false;                               // dg_result_limit: groups in the push-down order
   std::vector<int32_t> kinds;                         // DG_AGG_* of every aggregator (combine semantics)
+  dg_grouper_info grouper{};                          // what grouped it (dg_result_grouper_info)
   ~dg_result() {
     if (!ctx) return;
     std::lock_guard<std::mutex> g(ctx->mu);
@@ -3862,12 +3873,18 @@ extern "C" {
 
 int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb, dg_result** out,
                    dg_metrics* metrics) {
+  return dg_groupby_run_opts(segs, n, q, gb, nullptr, out, metrics);
+}
+
+int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb,
+                        const dg_groupby_opts* opts, dg_result** out, dg_metrics* metrics) {
   auto t0 = std::chrono::steady_clock::now();
   HostTrace ht;
   Context* ctx;
   int rc = check_segments(segs, n, &ctx);
   if (rc) return rc;
   if (!q || !gb || !out) return set_error(DG_ERR_ARG, "null argument");
+  if (opts && opts->grouper > DG_GROUPER_HASH) return set_error(DG_ERR_ARG, "unknown grouper %d", opts->grouper);
   dg_scan qs;
   Grain gr;
   rc = prepare_scan(q, &qs, &gr);
@@ -4064,6 +4081,27 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
     rc = sort_bufs(cs, total, ntiles, key_bits, na, &sb);
     if (rc) return rc;
   }
+  // The grouper (dg_groupby_opts): the hash table is sized for max_groups = the limit, capped at the
+  // call's elements and at the key space. Not eligible (the sort runs, same result): a floatSum plan
+  // (k_fsum_runs walks sorted runs), a 64-bit key (~0 marks an empty position), positions beyond 32 bits.
+  const GrouperChoice choice = resolve_grouper(opts, ctx->grouper, ctx->max_groups, getenv("DG_GROUPER"));
+  int64_t max_groups = std::max<int64_t>(total, 1);
+  if (choice.max_groups > 0) max_groups = std::min(max_groups, choice.max_groups);
+  if (key_bits < 62) max_groups = std::min<int64_t>(max_groups, (int64_t)1 << key_bits);
+  HashTable tab{};
+  const bool use_hash = choice.grouper == DG_GROUPER_HASH && !has_float_sum(plan) && key_bits <= 63 &&
+                        hash_capacity(max_groups) <= ((int64_t)1 << 31);
+  if (use_hash) {
+    tab.capacity = hash_capacity(max_groups);
+    tab.log2_capacity = bits_for(tab.capacity);
+    tab.max_groups = max_groups;
+    tab.keys = dev_take<uint64_t>(cs, (size_t)tab.capacity);
+    tab.slots = dev_take<uint64_t>(cs, (size_t)tab.capacity * rec);
+    tab.ctr = dev_take<unsigned long long>(cs, 4);
+    if (!tab.keys || !tab.slots || !tab.ctr)
+      return set_error(DG_ERR_OOM, "hash table of %lld slots x %d words", (long long)tab.capacity, rec + 1);
+    if (!call_err(cs, st)) return set_error(DG_ERR_OOM, "error word");
+  }
   uint32_t* h_n = host_take<uint32_t>(cs, 4);
   if (!h_n) return set_error(DG_ERR_OOM, "groupBy counters");
   DG_FLUSH(cs, st);
@@ -4086,12 +4124,33 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
   for (int i = 0; i < n && rows_elems; ++i) rows_elems = !cur[i].any || all_rows_in(i);
   launch_gb_keygen(d_jobs, d_tile, ntiles, &sb, plan, st, any_multi, rows_elems ? total : -1);
   phase_event(ctx->ev[5], st);
-  launch_radix_sort(&sb, key_bits, st);
-  phase_event(ctx->ev[6], st);
+  // The hash grouper: the elements aggregated into the HBM table (per tile in LDS first), then one
+  // read-back of the group count, which sizes the group sort and the result (cap = groups). In
+  // dg_metrics sort_ms is the insert and reduce_ms the collect + group sort + emit.
+  unsigned long long* h_ctr = nullptr;
+  if (use_hash) {
+    h_ctr = host_take<unsigned long long>(cs, 4);
+    if (!h_ctr) return set_error(DG_ERR_OOM, "groupBy counters");
+    launch_gb_hash_fill(tab, plan, st);
+    if (side) DG_HIP(hipStreamWaitEvent(st, ctx->side_ev[2], 0));  // the payload is decoded
+    launch_gb_hash_insert(&sb, sb.cap, tab, plan, cs->d_err, st);
+    phase_event(ctx->ev[6], st);
+    DG_HIP(hipMemcpyAsync(h_ctr, tab.ctr, 32, hipMemcpyDeviceToHost, st));
+    DG_HIP(hipMemcpyAsync(h_n, sb.n, 4, hipMemcpyDeviceToHost, st));  // selected rows
+    rc = finish_call(cs, st);
+    if (rc == DG_ERR_TABLE_FULL)
+      return set_error(DG_ERR_TABLE_FULL, "groupBy hash table full: more than %lld groups (bufferGrouperMaxSize; %lld slots)",
+                       (long long)tab.max_groups, (long long)tab.capacity);
+    if (rc) return rc;
+  } else {
+    launch_radix_sort(&sb, key_bits, st);
+    phase_event(ctx->ev[6], st);
+  }
   DG_CHECK_INTERRUPT(intr);
   // the result is laid out for the sort's capacity (>= the groups): the reduce counts the groups itself
-  // (look-back over tiles), so there is no host read-back between the sort and the reduce
-  const int64_t cap = std::max<int64_t>(sb.cap, 1);
+  // (look-back over tiles), so there is no host read-back between the sort and the reduce; the hash
+  // grouper knows its groups here
+  const int64_t cap = std::max<int64_t>(use_hash ? (int64_t)h_ctr[0] : sb.cap, 1);
   PendingResult res(new dg_result());
   res->ctx = ctx;
   res->ndims = nd;
@@ -4108,7 +4167,23 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
   res->cap = cap;
   if (!res->keys || !res->slots) return set_error(DG_ERR_OOM, "groupBy result of %lld records", (long long)cap);
   bool reduce_timed = false;
-  {
+  if (use_hash) {
+    const int64_t ngh = (int64_t)h_ctr[0];
+    phase_event(ctx->ev[7], st);
+    reduce_timed = true;
+    if (ngh > 0) {  // the groups' [key | table position] words, sorted by key, gather their records
+      SortBufs gsb;
+      rc = sort_bufs(cs, ngh, 1, key_bits, 0, &gsb, tab.log2_capacity);
+      if (rc) return rc;
+      launch_gb_hash_collect(tab, &gsb, ngh, st);
+      launch_radix_sort(&gsb, key_bits, st);
+      launch_gb_hash_emit(&gsb, ngh, tab, plan, res->keys, res->slots, cap, st);
+    }
+    res->grouper.grouper = DG_GROUPER_HASH;
+    res->grouper.table_slots = tab.capacity;
+    res->grouper.flushed_entries = (int64_t)h_ctr[1];
+    res->grouper.direct_elements = (int64_t)h_ctr[2];
+  } else {
     // run heads are only needed by the floatSum row-order pass
     uint32_t* head_pos = has_float_sum(plan) ? dev_take<uint32_t>(cs, (size_t)cap + 16) : nullptr;
     const size_t nt = (size_t)sb.ntiles_sort;  // one carry / open group per tile
@@ -4125,13 +4200,18 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
       if (plan.kind[a] == DG_AGG_FLOAT_SUM) launch_fsum_runs(d_jobs, n, ntiles, &sb, plan, a, head_pos, res->slots, cap, st);
   }
   phase_event(ctx->ev[4], st);
-  DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));  // selected rows, groups
+  if (!use_hash) DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));  // selected rows, groups
   ht.mark("reduce_launched");
   rc = finish_call(cs, st);  // (polls the cancel flag / timeout while the device works)
   if (rc) return rc;
   ht.mark("synced");
-  const int64_t nsel = h_n[0], ng = h_n[1];
+  const int64_t nsel = h_n[0], ng = use_hash ? (int64_t)h_ctr[0] : (int64_t)h_n[1];
+  // bufferGrouperMaxSize holds under either grouper (the hash grouper failed at its insert)
+  if (choice.max_groups > 0 && ng > choice.max_groups)
+    return set_error(DG_ERR_TABLE_FULL, "groupBy of %lld groups: more than %lld (bufferGrouperMaxSize)", (long long)ng,
+                     (long long)choice.max_groups);
   res->ngroups = ng;
+  res->grouper.max_groups = use_hash ? tab.max_groups : choice.max_groups;
   // The result was laid out for the call's rows; when the groups are far fewer (filtered or few-group
   // queries) it is compacted to them and the row-sized blocks go back to the context's cache.
   if (ng * 2 < cap && (size_t)cap * rec * 8 >= ((size_t)1 << 20)) {
@@ -4192,6 +4272,12 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
 }
 
 int64_t dg_result_groups(const dg_result* r) { return r ? r->ngroups : -1; }
+
+int dg_result_grouper_info(const dg_result* r, dg_grouper_info* out) {
+  if (!r || !out) return set_error(DG_ERR_ARG, "null argument");
+  *out = r->grouper;
+  return DG_OK;
+}
 
 int dg_result_fetch_groups(dg_result* r, int64_t start, int64_t count, int64_t* bucket_time, int32_t* ids,
                            uint64_t* values) {

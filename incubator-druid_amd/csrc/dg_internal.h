@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <atomic>
@@ -463,6 +464,10 @@ struct Context {
   hipEvent_t ovl_ev[2] = {};
   // dg_context_set_limit(DG_LIMIT_GROUP_ELEMENTS): most sort elements one groupBy call may build
   uint64_t max_elements = ~0ull;
+  // dg_context_set_limit(DG_LIMIT_GROUPER / DG_LIMIT_GROUPER_MAX_GROUPS): the default grouper of the
+  // context's groupBy calls and their bufferGrouperMaxSize (0: unlimited)
+  int32_t grouper = DG_GROUPER_SORT;
+  int64_t max_groups = 0;
   std::vector<std::shared_ptr<MergedDict>> dict_cache;  // most recent last
   // device blocks of groupBy results: live (size by pointer) and released for reuse
   std::map<void*, size_t> block_size;
@@ -712,6 +717,54 @@ void launch_soa_to_aos(const uint64_t* soa, int64_t cap, int64_t n, int rec, uin
 // a result laid out for `cap` records compacted to its n groups: keys [n], slots [rec][n] (16-byte copies)
 void launch_result_compact(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n, int rec, uint64_t* keys2,
                            uint64_t* slots2, hipStream_t s);
+// dg_hash.hip — the opt-in hash grouper (BufferHashGrouper.java:38-133 over ByteBufferHashTable.java:286-327):
+// an open-addressing table in HBM, empty key = ~0ull (keys of <= 63 bits), linear probing from a mixed hash.
+constexpr uint64_t kHashEmpty = ~0ull;
+constexpr int32_t kErrTableFull = 8;  // bit of the call's device error word (CallScratch::d_err)
+constexpr int kHashTile = 4096;       // keygen elements per insert workgroup
+struct HashTable {
+  uint64_t* keys;           // [capacity]
+  uint64_t* slots;          // [1 + naggs][capacity] (slot-major): rows, then the values in the device slot encoding
+  int64_t capacity;         // power of two
+  int log2_capacity;
+  int64_t max_groups;       // bufferGrouperMaxSize: a claim beyond it fails the call (Groupers.HASH_TABLE_FULL)
+  unsigned long long* ctr;  // [0] groups claimed, [1] LDS entries flushed, [2] elements that bypassed a full LDS table
+};
+// table slots for max_groups groups: the next power of two >= max_groups / 0.7 (ByteBufferHashTable's
+// default max load factor, AbstractBufferHashGrouper.DEFAULT_MAX_LOAD_FACTOR)
+inline int64_t hash_capacity(int64_t max_groups) {
+  int64_t c = 1;
+  while (c * 7 < max_groups * 10) c <<= 1;
+  return c;
+}
+// The grouper and group limit of one call: explicit opts first, then (grouper only) the DG_GROUPER
+// environment switch ("hash" / "sort", anything else ignored), then the context's defaults.
+// max_groups 0 = unlimited.
+struct GrouperChoice {
+  int32_t grouper;
+  int64_t max_groups;
+};
+inline GrouperChoice resolve_grouper(const dg_groupby_opts* opts, int32_t ctx_grouper, int64_t ctx_max_groups,
+                                     const char* env) {
+  GrouperChoice c{ctx_grouper, ctx_max_groups > 0 ? ctx_max_groups : 0};
+  if (env && !strcmp(env, "hash")) c.grouper = DG_GROUPER_HASH;
+  else if (env && !strcmp(env, "sort")) c.grouper = DG_GROUPER_SORT;
+  if (opts && opts->grouper >= 0) c.grouper = opts->grouper;
+  if (opts && opts->max_groups > 0) c.max_groups = opts->max_groups;
+  return c;
+}
+// keys = empty, slots = the aggregators' identities, counters = 0
+void launch_gb_hash_fill(const HashTable& ht, AggPlan plan, hipStream_t s);
+// the keygen's elements (sb, at most elem_cap of them) aggregated per tile in LDS and upserted into ht;
+// err: the call's device error word (kErrTableFull)
+void launch_gb_hash_insert(const SortBufs* sb, int64_t elem_cap, const HashTable& ht, AggPlan plan, int32_t* err,
+                           hipStream_t s);
+// occupied positions -> gsb's sort words [key | position] (or keys + refs), gsb->n[0] = their count (<= ng)
+void launch_gb_hash_collect(const HashTable& ht, SortBufs* gsb, int64_t ng, hipStream_t s);
+// the sorted words' table records -> out_keys[g], out_slots[s * cap + g] (rows, then ABI-encoded values)
+void launch_gb_hash_emit(const SortBufs* gsb, int64_t ng, const HashTable& ht, AggPlan plan, uint64_t* out_keys,
+                         uint64_t* out_slots, int64_t cap, hipStream_t s);
+
 // groups [start, start + count): key fields -> bucket index and merged ids (int32 per dimension)
 struct KeyLayout {
   int32_t ndims;

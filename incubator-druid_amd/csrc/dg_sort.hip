@@ -58,30 +58,6 @@ constexpr int kRsT = DG_RS_THREADS;
 constexpr int kRsW = kRsT / 64;  // waves of a scatter tile
 constexpr int kRsSPT = kRsTile / kRsT;
 
-// exclusive scan of one u32 per thread over an NT-thread workgroup; *total = workgroup sum
-template <int NT>
-__device__ __forceinline__ uint32_t block_scan_u32(uint32_t v, uint32_t* total, uint32_t* s_tmp) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_tmp[wave] = x;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint32_t y = s_tmp[w];
-    off += w < wave ? y : 0u;
-    tot += y;
-  }
-  __syncthreads();
-  *total = tot;
-  return off + x - v;
-}
-
 template <int NT>
 __device__ __forceinline__ uint64_t block_scan_u64(uint64_t v, uint64_t* total, uint64_t* s_tmp) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -886,31 +862,6 @@ __global__ __launch_bounds__(kST) void k_run_mark(const uint64_t* __restrict__ k
 void launch_run_mark(SortBufs* sb, uint32_t* head_pos, hipStream_t s) {
   hipLaunchKernelGGL(k_run_mark, dim3(sb->ntiles_sort), dim3(kST), 0, s, sb->keys[sb->cur], sb->n, sb->ref_bits,
                      sb->run_cnt, head_pos);
-}
-
-// ------------------------------------------------------------------------------------------------
-// finalize: device slot encoding -> the ABI's (int64 / double / float32 in the low 4 bytes)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t finalize_dev(int kind, uint64_t s) {
-  switch (kind) {
-    case DG_AGG_COUNT:
-    case DG_AGG_LONG_SUM:
-    case DG_AGG_DOUBLE_SUM: return s;
-    case DG_AGG_FLOAT_SUM: return (uint64_t)__float_as_uint((float)__longlong_as_double((long long)s));
-    case DG_AGG_LONG_MIN:
-    case DG_AGG_LONG_MAX: return s ^ kSign;
-    case DG_AGG_DOUBLE_MIN:
-    case DG_AGG_DOUBLE_MAX: {
-      const bool nan = kind == DG_AGG_DOUBLE_MIN ? s == 0 : s == ~0ull;
-      const double d = nan ? __longlong_as_double(0x7ff8000000000000ll) : unord_key(s);
-      return (uint64_t)__double_as_longlong(d);
-    }
-    default: {
-      const bool nan = kind == DG_AGG_FLOAT_MIN ? s == 0 : s == ~0ull;
-      const float f = nan ? __uint_as_float(0x7fc00000u) : (float)unord_key(s);
-      return (uint64_t)__float_as_uint(f);
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------

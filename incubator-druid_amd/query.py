@@ -929,6 +929,18 @@ class GroupByQuery(BaseQuery):
             return v.strip().lower() == "true"
         return bool(v)
 
+    def force_hash_aggregation(self) -> bool:
+        """GroupByQueryConfig.CTX_KEY_FORCE_HASH_AGGREGATION (GroupByQueryConfig.java:35-40,179-200)."""
+        return self._ctx_bool("forceHashAggregation", False)
+
+    def buffer_grouper_max_size(self) -> int:
+        """The context's bufferGrouperMaxSize (GroupByQueryConfig.CTX_KEY_BUFFER_GROUPER_MAX_SIZE): the most
+        groups a grouper may hold; 0 = not set (Integer.MAX_VALUE in the reference)."""
+        v = (self.context or {}).get("bufferGrouperMaxSize")
+        if v is None or isinstance(v, bool):
+            return 0
+        return max(int(v), 0)
+
     def order_by_dims(self) -> Optional[List[int]]:
         """Dimension index of every ORDER BY column (OrderByColumnSpec.getDimIndexForOrderBy), or None
         when one sorts on a non-grouping field (DefaultLimitSpec.sortingOrderHasNonGroupingFields)."""

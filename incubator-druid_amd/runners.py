@@ -786,6 +786,13 @@ class GroupByResult:
             pool.hold(part)
         return part
 
+    def grouper_info(self) -> Dict:
+        """What grouped this result (dg_result_grouper_info): the grouper that ran (N.GROUPER_*), its HBM
+        table's slots, the group limit in force and the hash insert's LDS flush / direct counts."""
+        info = N.dg_grouper_info()
+        N.check(N.lib().dg_result_grouper_info(self.handle, ctypes.byref(info)))
+        return info.as_dict()
+
     def apply_limit_push_down(self) -> bool:
         """LimitedBufferHashGrouper's outcome on the device (dg_result_limit): when the query pushes
         its limit down (GroupByQuery.isApplyLimitPushDown), keep the first `limit` groups in the
@@ -833,6 +840,20 @@ def _beyond_bmp_low(values) -> bool:
     return any(v is not None and any(ord(ch) > 0xD7FF for ch in v) for v in values)
 
 
+def grouper_options(query: Q.GroupByQuery) -> Optional[Tuple[int, int]]:
+    """The query context's grouper keys as dg_groupby_opts fields (grouper, max_groups), or None when
+    the query names neither (the call then takes the context's defaults): forceHashAggregation ->
+    DG_GROUPER_HASH (false: the sort, explicitly), bufferGrouperMaxSize -> max_groups
+    (GroupByQueryConfig.java:35-40,179-200). -1 / 0 leave a field to the context's default."""
+    ctx = query.context or {}
+    if "forceHashAggregation" not in ctx and "bufferGrouperMaxSize" not in ctx:
+        return None
+    grouper = -1
+    if "forceHashAggregation" in ctx:
+        grouper = N.GROUPER_HASH if query.force_hash_aggregation() else N.GROUPER_SORT
+    return grouper, query.buffer_grouper_max_size()
+
+
 def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
                 stats: Optional[RunStats] = None, limit_push_down: bool = False,
                 cancel: Optional[ctypes.c_int32] = None) -> GroupByResult:
@@ -853,8 +874,14 @@ def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     res = ctypes.c_void_p()
     m = N.dg_metrics()
     t0 = time.perf_counter()
-    N.check(N.lib().dg_groupby_run(_handles(segments), len(segments), ctypes.byref(scan), ctypes.byref(g),
-                                   ctypes.byref(res), ctypes.byref(m)))
+    opts = grouper_options(query)
+    if opts is None:
+        N.check(N.lib().dg_groupby_run(_handles(segments), len(segments), ctypes.byref(scan), ctypes.byref(g),
+                                       ctypes.byref(res), ctypes.byref(m)))
+    else:
+        o = N.dg_groupby_opts(opts[0], 0, opts[1])
+        N.check(N.lib().dg_groupby_run_opts(_handles(segments), len(segments), ctypes.byref(scan), ctypes.byref(g),
+                                            ctypes.byref(o), ctypes.byref(res), ctypes.byref(m)))
     if stats is not None:
         stats.add(m, (t0, time.perf_counter()))
     out = GroupByResult(res, query)
