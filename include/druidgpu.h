@@ -214,7 +214,8 @@ typedef struct {
                                 read-back, collect, group sort and emit) */
   int32_t sort_passes;
   int32_t key_bits;
-  int64_t groups;            /* merged groups */
+  int64_t groups;            /* groupBy: merged groups; topN: the candidates its selection kept over every result
+                                list (ids whose metric key >= the list's K-th largest key) */
   /* groupBy: payload columns decoded in place on the side stream, overlapping the key build + sort */
   double decode_side_ms;     /* device time of those decodes (their own stream) */
   int64_t bytes_side;        /* their algorithmic bytes (part of bytes_read) */

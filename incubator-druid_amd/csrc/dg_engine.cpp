@@ -3278,6 +3278,7 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
     const int i = sel_seg[k];
     m.selected_rows += (int64_t)h_state[sel_words * k + 1];
     const int nc = h_ncand[k];
+    m.groups += nc;  // (what the radix selection kept: `threshold` plus the K-th key's ties when its bound is exact)
     struct E {
       uint64_t key;
       int32_t id;
