@@ -28,6 +28,11 @@
  *   dg_groupby_run_opts      <- the same under GroupByQueryConfig's forceHashAggregation / bufferGrouperMaxSize
  *                               (query/groupby/GroupByQueryConfig.java:35-40): BufferHashGrouper over ByteBufferHashTable
  *                               (epinephelinae/BufferHashGrouper.java:38-133, ByteBufferHashTable.java:286-327)
+ *   dg_search_run            <- SearchQueryRunnerFactory.createRunner(segment).run: the counting of SearchQueryRunner.run
+ *                               (query/search/SearchQueryRunner.java:207-260) under UseIndexesStrategy.getExecutionPlan
+ *                               (UseIndexesStrategy.java:66-109): IndexOnlyExecutor.execute (:236-281) over
+ *                               makeTimeFilteredBitmap (:143-219), or CursorBasedExecutor with
+ *                               StringSearchColumnSelectorStrategy.updateSearchResultSet (SearchQueryRunner.java:118-141)
  *   dg_result_*              <- the merged grouper's sorted iterator (ConcurrentGrouper.iterator(true))
  *   dg_result_export / dg_keys_partition / dg_merge
  *                            <- QueryRunnerFactory.mergeRunners across devices (query/QueryRunnerFactory.java:62):
@@ -374,6 +379,50 @@ typedef struct {
 
 int dg_topn_merge(dg_segment* const* segs, const dg_scan* scan, const dg_topn* topn, const dg_topn_lists* in,
                   int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values);
+
+/* ---- search ----
+ * Per-value hit counts of a search query (query/search/SearchQueryRunner.java:207-260). The caller
+ * evaluates SearchQuerySpec.accept over the dictionaries it exports with dg_segment_dim_dictionary (the
+ * Java shim with its own spec objects and extraction functions) and passes, per search dimension and
+ * segment, the accepted segment-local dictionary ids; the engine counts, for each, the rows it occurs in
+ * inside the selection S = filter AND rows whose time lies in [interval_start, interval_end):
+ *   DG_SEARCH_PLAN_INDEX   IndexOnlyExecutor.execute (UseIndexesStrategy.java:236-281): |bitmap(id) AND S|, or the
+ *                          bitmap's size when there is no filter and the interval covers the segment's rows. A
+ *                          multi-value row counts once per distinct value. Taken for a dimension with a bitmap index
+ *                          when the filter is null or runs on bitmap indexes alone (UseIndexesStrategy.java:87-98).
+ *                          The interval rows are found by a per-row time test, which equals the reference's binary
+ *                          search over __time (makeTimeFilteredBitmap, :164-219) on time-sorted segments, the only
+ *                          kind IndexMergerV9 writes.
+ *   DG_SEARCH_PLAN_CURSOR  CursorBasedExecutor: every occurrence of an accepted value in a selected row counts one
+ *                          (StringSearchColumnSelectorStrategy, SearchQueryRunner.java:118-141: a row [a, a] counts 2).
+ *                          Taken when a filter leaf is a row post-filter (a numeric column), when the segment has no
+ *                          bitmap index (dg_segment_from_rows), or with DG_SEARCH_CURSOR_ONLY (CursorOnlyStrategy).
+ *                          The counts are those of the full scan: the reference's early exit once its map holds
+ *                          `limit` hits (:135-137) stops at a row the counts then depend on, so a caller that finds
+ *                          at least `limit` distinct hits under this plan keeps its CPU engine.
+ *   DG_SEARCH_PLAN_NONE    the column is missing in the segment or no id was passed: nothing to count.
+ * scan supplies the filter, the interval, cancel and timeout_ms; its aggregators and granularity are ignored
+ * (n_aggs == 0 is allowed). out_counts is flat in (segment, dimension, id) order, the sum of every n_ids
+ * entries; zero counts are the caller's to drop, and the limit, the comparator-keyed map and the `remain`
+ * arithmetic of SearchQueryRunner.run are the caller's too (out_plan[seg * n_dims + d] tells which limit rule
+ * applies). Errors before any launch: ids not strictly ascending or not below the cardinality -> DG_ERR_ARG; a
+ * LONG / FLOAT / DOUBLE column as a search dimension -> DG_ERR_UNSUPPORTED (its values have no dictionary).
+ * Metrics: segment_rows, pre_filtered_rows, selected_rows, bitmap_bytes, bytes_read (serialized bitmap bytes +
+ * N/8 of selection per accepted value, or the columns scanned), bitmap_ms (the selection), aggregate_ms (the
+ * counting), decode_ms, total_ms. */
+#define DG_SEARCH_USE_INDEXES 0   /* UseIndexesStrategy: index plan where the reference takes it, else cursor */
+#define DG_SEARCH_CURSOR_ONLY 1
+#define DG_SEARCH_PLAN_NONE   0   /* column missing in this segment / nothing accepted */
+#define DG_SEARCH_PLAN_INDEX  1
+#define DG_SEARCH_PLAN_CURSOR 2
+typedef struct {
+  const char* dimension;
+  const int32_t* const* ids;  /* [n_segs] accepted segment-local dictionary ids, strictly ascending */
+  const int32_t* n_ids;       /* [n_segs] */
+} dg_search_dim;
+typedef struct { const dg_search_dim* dims; int32_t n_dims; int32_t strategy; } dg_search;
+int dg_search_run(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_search* s,
+                  int64_t* out_counts, int32_t* out_plan, dg_metrics* metrics);
 
 /* ---- groupBy (v2) ---- */
 /* GroupByStrategyV2.mergeRunners over the call's segments: every segment's rows grouped

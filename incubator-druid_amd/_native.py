@@ -26,6 +26,8 @@ ORDER = {"lexicographic": 0, "numeric": 1}
 LIMIT_GROUP_ELEMENTS = 1
 LIMIT_GROUPER, LIMIT_GROUPER_MAX_GROUPS = 2, 3
 GROUPER_SORT, GROUPER_HASH = 0, 1
+SEARCH_USE_INDEXES, SEARCH_CURSOR_ONLY = 0, 1
+SEARCH_PLAN_NONE, SEARCH_PLAN_INDEX, SEARCH_PLAN_CURSOR = 0, 1, 2
 ERR_TABLE_FULL = 5
 
 
@@ -120,6 +122,14 @@ class dg_grouper_info(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class dg_search_dim(ctypes.Structure):
+    _fields_ = [("dimension", ctypes.c_char_p), ("ids", ctypes.c_void_p), ("n_ids", ctypes.c_void_p)]
+
+
+class dg_search(ctypes.Structure):
+    _fields_ = [("dims", ctypes.POINTER(dg_search_dim)), ("n_dims", ctypes.c_int32), ("strategy", ctypes.c_int32)]
+
+
 class dg_record_layout(ctypes.Structure):
     _fields_ = [("n_aggs", ctypes.c_int32), ("kinds", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("record_size", ctypes.c_int32), ("big_endian", ctypes.c_int32)]
@@ -158,7 +168,7 @@ EXPORTS = [
     "dg_merge", "dg_records_pack", "dg_debug_lz4_decode", "dg_result_limit",
     "dg_segment_from_rows", "dg_context_set_limit", "dg_groupby_merge_devices", "dg_timeseries_merge",
     "dg_debug_lz4_classify", "dg_host_alloc", "dg_host_free", "dg_set_phase_timing", "dg_debug_probe",
-    "dg_groupby_run_opts", "dg_result_grouper_info",
+    "dg_groupby_run_opts", "dg_result_grouper_info", "dg_search_run",
 ]
 
 _lib = None
@@ -212,6 +222,7 @@ def lib():
         "dg_groupby_run_opts": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_groupby), P(dg_groupby_opts), P(vp),
                                                P(dg_metrics)]),
         "dg_result_grouper_info": (ctypes.c_int, [vp, P(dg_grouper_info)]),
+        "dg_search_run": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_search), vp, vp, P(dg_metrics)]),
         "dg_result_groups": (i64, [vp]),
         "dg_result_fetch_groups": (ctypes.c_int, [vp, i64, i64, vp, vp, vp]),
         "dg_result_fetch_rows": (ctypes.c_int, [vp, i64, i64, vp]),

@@ -3461,6 +3461,287 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// search
+// ------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace dg {
+
+// Filter.supportsBitmapIndex over the tree (UseIndexesStrategy.java:87-98): a leaf on a numeric column is
+// a row post-filter, every other leaf (a missing column included: its index is the all-null one) runs on
+// a bitmap index
+static bool filter_on_bitmaps(const Segment* seg, const dg_filter* nodes, int n) {
+  for (int i = 0; i < n; ++i) {
+    const dg_filter& f = nodes[i];
+    if (f.kind != DG_F_SELECTOR && f.kind != DG_F_IN && f.kind != DG_F_BOUND) continue;
+    const Column* c = f.dimension ? seg->find(f.dimension) : nullptr;
+    if (c && c->type != DG_COL_STRING) return false;
+  }
+  return true;
+}
+
+}  // namespace dg
+
+extern "C" {
+
+int dg_search_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_search* s, int64_t* out_counts,
+                  int32_t* out_plan, dg_metrics* metrics) {
+  auto t0 = std::chrono::steady_clock::now();
+  Context* ctx;
+  int rc = check_segments(segs, n, &ctx);
+  if (rc) return rc;
+  if (!q || !s || !out_counts || !out_plan) return set_error(DG_ERR_ARG, "null argument");
+  if (s->n_dims < 0 || (s->n_dims > 0 && !s->dims)) return set_error(DG_ERR_ARG, "search dimensions");
+  if (s->strategy != DG_SEARCH_USE_INDEXES && s->strategy != DG_SEARCH_CURSOR_ONLY)
+    return set_error(DG_ERR_ARG, "search strategy %d", s->strategy);
+  // the scan without its granularity and aggregators: one cursor over the interval
+  dg_scan qs = *q;
+  qs.period_ms = 0;
+  qs.origin_ms = 0;
+  qs.bucket_starts = nullptr;
+  qs.n_bucket_starts = 0;
+  qs.seg_bounds = nullptr;
+  qs.descending = 0;
+  qs.aggs = nullptr;
+  qs.n_aggs = 0;
+  q = &qs;
+  const Grain gr;
+  const int nd = s->n_dims;
+  // every argument is checked before anything is launched
+  std::vector<int64_t> base((size_t)n * nd + 1, 0);  // first count of (segment, dimension)
+  std::vector<const Column*> cols((size_t)n * nd, nullptr);
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    const Segment* seg = reinterpret_cast<const Segment*>(segs[i]);
+    for (int d = 0; d < nd; ++d) {
+      const dg_search_dim& sd = s->dims[d];
+      if (!sd.dimension || !sd.n_ids || !sd.ids) return set_error(DG_ERR_ARG, "search dimension %d", d);
+      const int32_t k = sd.n_ids[i];
+      const int32_t* ids = sd.ids[i];
+      if (k < 0 || (k > 0 && !ids)) return set_error(DG_ERR_ARG, "ids of dimension %s", sd.dimension);
+      const Column* c = seg->find(sd.dimension);
+      if (c && (c->type == DG_COL_LONG || c->type == DG_COL_FLOAT || c->type == DG_COL_DOUBLE))
+        return set_error(DG_ERR_UNSUPPORTED, "search dimension %s is a numeric column", sd.dimension);
+      if (c && c->type != DG_COL_STRING)
+        return set_error(DG_ERR_UNSUPPORTED, "search dimension %s has an unsupported type", sd.dimension);
+      const int64_t card = c ? (int64_t)c->dict.size() : 1;  // (a missing column: its only value is null, id 0)
+      for (int32_t x = 0; x < k; ++x) {
+        if (ids[x] < 0 || ids[x] >= card)
+          return set_error(DG_ERR_ARG, "id %d of dimension %s is not below the cardinality %lld", ids[x], sd.dimension,
+                           (long long)card);
+        if (x > 0 && ids[x] <= ids[x - 1])
+          return set_error(DG_ERR_ARG, "ids of dimension %s are not strictly ascending", sd.dimension);
+      }
+      cols[(size_t)i * nd + d] = c;
+      base[(size_t)i * nd + d] = total;
+      total += k;
+    }
+  }
+  base[(size_t)n * nd] = total;
+  if (total > (int64_t)INT32_MAX) return set_error(DG_ERR_UNSUPPORTED, "%lld accepted values in one call", (long long)total);
+  CallGuard g(ctx);
+  CallScratch* cs = g.cs;
+  Interrupt intr(q, t0);
+  cs->intr = &intr;
+  hipStream_t st = ctx->stream;
+  dg_metrics m;
+  memset(&m, 0, sizeof m);
+  for (int64_t x = 0; x < total; ++x) out_counts[x] = 0;
+  // the counts in HBM (zeroed) and the selected-row counters of the time tests
+  unsigned long long* d_counts = dev_take<unsigned long long>(cs, (size_t)std::max<int64_t>(total, 1));
+  unsigned long long* h_counts = host_take<unsigned long long>(cs, (size_t)std::max<int64_t>(total, 1));
+  unsigned long long* d_sel;
+  unsigned long long* z_sel = up_take<unsigned long long>(cs, n, &d_sel, st);
+  unsigned long long* h_sel = host_take<unsigned long long>(cs, n);
+  if (!d_counts || !h_counts || !z_sel || !h_sel) return set_error(DG_ERR_OOM, "search counts");
+  memset(z_sel, 0, 8 * (size_t)n);
+  DG_HIP(hipMemsetAsync(d_counts, 0, 8 * (size_t)std::max<int64_t>(total, 1), st));
+  struct SegPlan {
+    bool live = false, timed = false;
+    uint32_t* filter_bits = nullptr;
+    uint32_t* sel = nullptr;  // S (null: every row)
+    ColView time;
+    int64_t t_lo = 0, t_hi = 0;
+    const unsigned long long* pre = nullptr;
+  };
+  std::vector<SegPlan> sp(n);
+  DecodeBatch db;
+  decode_events(ctx, &db, false);
+  std::vector<SearchJob> cj_small, cj_large, rj_whole, rj_piece;
+  struct HistPlan {
+    SearchHist h;
+    const int32_t* d_ids;
+    int n_ids;
+    int64_t out;
+  };
+  std::vector<HistPlan> hists;
+  int64_t bitmap_read = 0, sel_read = 0;
+  phase_event(ctx->ev[0], st);
+  for (int i = 0; i < n; ++i) {
+    Segment* seg = reinterpret_cast<Segment*>(segs[i]);
+    m.segment_rows += seg->nrows;
+    const bool on_bitmaps = !q->filter || q->n_filter <= 0 || filter_on_bitmaps(seg, q->filter, q->n_filter);
+    for (int d = 0; d < nd; ++d) {
+      const Column* c = cols[(size_t)i * nd + d];
+      const int32_t k = s->dims[d].n_ids[i];
+      int plan = DG_SEARCH_PLAN_NONE;
+      if (c && k > 0)
+        plan = (s->strategy == DG_SEARCH_CURSOR_ONLY || !c->has_bitmaps || !on_bitmaps) ? DG_SEARCH_PLAN_CURSOR
+                                                                                         : DG_SEARCH_PLAN_INDEX;
+      out_plan[(size_t)i * nd + d] = plan;
+    }
+    const Cursors cu = plan_cursors(seg, i, q, gr);
+    if (!cu.any) continue;  // no row of the segment lies in the interval: every count stays 0
+    SegPlan& p = sp[i];
+    p.live = true;
+    // (the filter is built even when nothing is counted: it is validated, and its rows are the metrics')
+    rc = build_bitset(seg, cs, q->filter, q->n_filter, &p.filter_bits, &p.pre, st);
+    if (rc) return rc;
+    p.sel = p.filter_bits;
+    if (cu.need_time) {
+      const Column* tcol = seg->find("__time");
+      if (!tcol) return set_error(DG_ERR_FORMAT, "segment without __time");
+      const std::vector<int64_t> tb = time_block_buckets(seg, tcol, cu, 0, gr);
+      rc = time_view(tcol, tb, cs, &db, &p.time, st);
+      if (rc) return rc;
+      p.sel = dev_take<uint32_t>(cs, (size_t)((seg->nrows + 31) / 32) + 2);
+      if (!p.sel) return set_error(DG_ERR_OOM, "selection bitset");
+      p.timed = true;
+      p.t_lo = cu.t_lo;
+      p.t_hi = cu.t_hi;
+      cs->bitmap_bytes += (seg->nrows + 31) / 32 * 4 * (p.filter_bits ? 2 : 1);
+    }
+    for (int d = 0; d < nd; ++d) {
+      const int plan = out_plan[(size_t)i * nd + d];
+      if (plan == DG_SEARCH_PLAN_NONE) continue;
+      const Column* c = cols[(size_t)i * nd + d];
+      const int32_t k = s->dims[d].n_ids[i];
+      const int32_t* ids = s->dims[d].ids[i];
+      const int64_t out0 = base[(size_t)i * nd + d];
+      if (plan == DG_SEARCH_PLAN_INDEX) {
+        const bool split = !c->bm_piece_first.empty();
+        const uint8_t* bm = c->bm_bytes.as<uint8_t>();
+        SearchJob j;
+        memset(&j, 0, sizeof j);
+        j.S = p.sel;
+        j.nrows = seg->nrows;
+        for (int32_t x = 0; x < k; ++x) {
+          const int32_t id = ids[x];
+          if (c->bm_len[id] == 0) continue;
+          bitmap_read += c->bm_len[id];
+          if (p.sel) sel_read += (seg->nrows + 7) / 8;  // (no selection bitset: the bitmap's own cardinality)
+          j.slot = (int32_t)(out0 + x);
+          if (split && c->bm_piece_first[id + 1] > c->bm_piece_first[id]) {  // a long bitmap: its pieces
+            for (int32_t pq = c->bm_piece_first[id]; pq < c->bm_piece_first[id + 1]; ++pq) {
+              const BmPiece& pc = c->bm_pieces[pq];
+              j.data = bm + pc.off;
+              j.row0 = pc.row0;
+              j.len = pc.len;
+              j.info = pc.info;
+              (c->bitmap_roaring ? rj_piece : cj_large).push_back(j);
+            }
+            continue;
+          }
+          j.data = bm + c->bm_off[id];
+          j.row0 = 0;
+          j.len = c->bm_len[id];
+          j.info = 0;
+          if (c->bitmap_roaring) rj_whole.push_back(j);
+          else (j.len <= 64 * 4 ? cj_small : cj_large).push_back(j);
+        }
+      } else {
+        HistPlan hp;
+        memset(&hp.h, 0, sizeof hp.h);
+        hp.h.offs.kind = VIEW_ABSENT;
+        rc = c->multi_value ? multi_view(c, cs, &db, &hp.h.vals, &hp.h.offs, st) : column_view(c, cs, &db, &hp.h.vals, st);
+        if (rc) return rc;
+        const size_t card = c->dict.size();
+        uint64_t* d_acc;
+        uint64_t* h_acc = up_take<uint64_t>(cs, (card + 63) / 64, &d_acc, st);
+        int32_t* d_ids;
+        int32_t* h_ids = up_take<int32_t>(cs, k, &d_ids, st);
+        unsigned long long* hist = dev_take<unsigned long long>(cs, card);
+        if (!h_acc || !h_ids || !hist) return set_error(DG_ERR_OOM, "search histogram");
+        memset(h_acc, 0, 8 * ((card + 63) / 64));
+        for (int32_t x = 0; x < k; ++x) h_acc[ids[x] >> 6] |= 1ull << (ids[x] & 63);
+        memcpy(h_ids, ids, 4 * (size_t)k);
+        DG_HIP(hipMemsetAsync(hist, 0, 8 * card, st));
+        hp.h.S = p.sel;
+        hp.h.accept = d_acc;
+        hp.h.hist = hist;
+        hp.h.nrows = seg->nrows;
+        hp.h.nvals = c->multi_value ? (int64_t)c->data.total : seg->nrows;
+        hp.h.card = (uint32_t)card;
+        hp.d_ids = d_ids;
+        hp.n_ids = k;
+        hp.out = out0;
+        hists.push_back(hp);
+        sel_read += (seg->nrows + 7) / 8;
+      }
+    }
+  }
+  DG_CHECK_INTERRUPT(intr);
+  // the job tables ride the same staged upload as the decoders' tables
+  const int ncj = (int)(cj_small.size() + cj_large.size()), nrj = (int)(rj_whole.size() + rj_piece.size());
+  SearchJob *d_cj = nullptr, *d_rj = nullptr;
+  if (ncj) {
+    SearchJob* h = up_take<SearchJob>(cs, ncj, &d_cj, st);
+    if (!h) return set_error(DG_ERR_OOM, "search jobs");
+    if (!cj_small.empty()) memcpy(h, cj_small.data(), sizeof(SearchJob) * cj_small.size());
+    if (!cj_large.empty()) memcpy(h + cj_small.size(), cj_large.data(), sizeof(SearchJob) * cj_large.size());
+  }
+  int32_t* d_err = nullptr;
+  if (nrj) {
+    SearchJob* h = up_take<SearchJob>(cs, nrj, &d_rj, st);
+    d_err = call_err(cs, st);
+    if (!h || !d_err) return set_error(DG_ERR_OOM, "search jobs");
+    if (!rj_whole.empty()) memcpy(h, rj_whole.data(), sizeof(SearchJob) * rj_whole.size());
+    if (!rj_piece.empty()) memcpy(h + rj_whole.size(), rj_piece.data(), sizeof(SearchJob) * rj_piece.size());
+  }
+  phase_event(ctx->ev[1], st);
+  rc = run_decodes(cs, &db, st);
+  if (rc) return rc;
+  phase_event(ctx->ev[2], st);
+  DG_CHECK_INTERRUPT(intr);
+  DG_FLUSH(cs, st);
+  for (int i = 0; i < n; ++i)
+    if (sp[i].timed)
+      launch_search_time_and(sp[i].time, sp[i].filter_bits, reinterpret_cast<Segment*>(segs[i])->nrows, sp[i].t_lo,
+                             sp[i].t_hi, sp[i].sel, d_sel + i, st);
+  phase_event(ctx->ev[3], st);
+  DG_CHECK_INTERRUPT(intr);
+  launch_search_concise_count(d_cj, (int)cj_small.size(), ncj, d_counts, st);
+  launch_search_roaring_count(d_rj, (int)rj_whole.size(), nrj, d_counts, d_err, st);
+  for (const HistPlan& hp : hists) launch_search_hist(hp.h, hp.d_ids, hp.n_ids, d_counts + hp.out, st);
+  phase_event(ctx->ev[4], st);
+  if (total) DG_HIP(hipMemcpyAsync(h_counts, d_counts, 8 * (size_t)total, hipMemcpyDeviceToHost, st));
+  cs->late.push_back({h_sel, d_sel, 8 * (size_t)n});
+  rc = finish_call(cs, st);
+  if (rc) return rc;
+  for (int64_t x = 0; x < total; ++x) out_counts[x] = (int64_t)h_counts[x];
+  for (int i = 0; i < n; ++i) {
+    if (!sp[i].live) continue;
+    const int64_t pre = sp[i].pre ? (int64_t)*sp[i].pre : reinterpret_cast<Segment*>(segs[i])->nrows;
+    m.pre_filtered_rows += pre;
+    m.selected_rows += sp[i].timed ? (int64_t)h_sel[i] : pre;
+  }
+  float f1 = 0, f2 = 0, f3 = 0, f4 = 0;
+  phase_elapsed(&f1, ctx->ev[0], ctx->ev[1]);
+  phase_elapsed(&f2, ctx->ev[1], ctx->ev[2]);
+  phase_elapsed(&f3, ctx->ev[2], ctx->ev[3]);
+  phase_elapsed(&f4, ctx->ev[3], ctx->ev[4]);
+  m.bitmap_ms = f1 + f3;  // the filter's bitset + the interval test
+  m.decode_ms = f2;
+  m.aggregate_ms = f4;
+  m.bitmap_bytes = cs->bitmap_bytes + bitmap_read;
+  m.bytes_read = bitmap_read + sel_read + db.bytes;
+  decode_metrics(db, DecodeBatch(), &m, nullptr);
+  m.total_ms = ms_since(t0);
+  if (metrics) *metrics = m;
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // topN merge (TopNBinaryFn fold)
 // ------------------------------------------------------------------------------------------------
 }  // extern "C"

@@ -563,6 +563,43 @@ void launch_roaring_or(const uint8_t* bm_base, const int64_t* d_off, const int32
                        int nbitmaps, uint32_t* const* d_sets, int32_t* d_err, int64_t limit_bits, hipStream_t s);
 void launch_filter_eval(const int32_t* d_prog, int prog_len, uint32_t* const* d_sets, uint32_t* out, int64_t nrows,
                         unsigned long long* d_count, hipStream_t s);
+// ---- search query (dg_search.hip) ----
+// One intersect-and-count job: a serialized bitmap (or a piece of one split at attach) of an accepted
+// dictionary value, counted inside the selection bitset S of its segment into counts[slot].
+struct SearchJob {
+  const uint8_t* data;  // the bitmap's / piece's bytes in HBM
+  const uint32_t* S;    // selection bitset of the segment's rows; null = every row
+  int64_t nrows;        // rows of the segment (rows at or beyond it count nothing)
+  int64_t row0;         // first row the piece covers (0 for a whole bitmap)
+  int32_t len;          // bytes
+  int32_t info;         // Roaring container piece: BmPiece::info
+  int32_t slot;         // index into the call's counts
+  int32_t pad;
+};
+constexpr int kSearchLdsCard = 8192;  // dictionaries up to this count in LDS (k_search_hist)
+// the cursor plan of one (segment, dimension): occurrences of accepted ids over the rows S selects
+struct SearchHist {
+  ColView vals;            // dictionary ids (multi-value: the value lists)
+  ColView offs;            // multi-value: rows + 1 offsets into vals; VIEW_ABSENT otherwise
+  const uint32_t* S;       // null = every row
+  const uint64_t* accept;  // bit per dictionary id
+  unsigned long long* hist;  // [card] counters, zeroed
+  int64_t nrows;
+  int64_t nvals;           // multi-value: values stored
+  uint32_t card;
+  uint32_t pad;
+};
+// out = `in` (null = all rows) AND rows whose time lies in [t_lo, t_hi); *d_count += rows selected
+void launch_search_time_and(ColView time, const uint32_t* in, int64_t nrows, int64_t t_lo, int64_t t_hi, uint32_t* out,
+                            unsigned long long* d_count, hipStream_t s);
+// jobs [0, n_small): at most 64 words, one wave each; [n_small, n_jobs): one workgroup each
+void launch_search_concise_count(const SearchJob* d_jobs, int n_small, int n_jobs, unsigned long long* d_counts,
+                                 hipStream_t s);
+// jobs [0, n_whole): whole bitmaps, one workgroup each; [n_whole, n_jobs): single containers, one wave each
+void launch_search_roaring_count(const SearchJob* d_jobs, int n_whole, int n_jobs, unsigned long long* d_counts,
+                                 int32_t* d_err, hipStream_t s);
+// the histogram of one (segment, dimension) and the gather of its accepted ids' counters into d_out[0, n_ids)
+void launch_search_hist(const SearchHist& h, const int32_t* d_ids, int n_ids, unsigned long long* d_out, hipStream_t s);
 // Row predicate of a filter on a numeric column: the reference evaluates it per row as a post-filter
 // (QueryableIndexStorageAdapter.makeCursors :244-260 -> FilteredOffset.java:40-105) through the
 // column's ValueMatcher ({Long,Float,Double}ValueMatcherColumnSelectorStrategy, the filters'

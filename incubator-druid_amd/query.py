@@ -10,8 +10,8 @@ fed in unchanged (``Query.from_json``):
 * aggregators: query/aggregation/{Count,LongSum,DoubleSum,FloatSum,LongMin,LongMax,DoubleMin,
   DoubleMax,FloatMin,FloatMax}AggregatorFactory.java (combine / comparator / initial values)
 * queries: query/timeseries/TimeseriesQuery.java, query/topn/TopNQuery.java,
-  query/groupby/GroupByQuery.java; topN metric specs NumericTopNMetricSpec / InvertedTopNMetricSpec
-  / DimensionTopNMetricSpec.
+  query/groupby/GroupByQuery.java, query/search/SearchQuery.java; topN metric specs
+  NumericTopNMetricSpec / InvertedTopNMetricSpec / DimensionTopNMetricSpec.
 
 Only the null-handling mode the reference defaults to is modelled
 (``druid.generic.useDefaultValueForNull=true``, common/config/NullHandling.java:34,54):
@@ -983,6 +983,92 @@ class GroupByQuery(BaseQuery):
         return js
 
 
+SEARCH_SPEC_TYPES = ("contains", "insensitive_contains", "fragment", "regex", "all")
+SEARCH_SORTS = ("lexicographic", "alphanumeric", "numeric", "strlen")
+SEARCH_STRATEGIES = ("useIndexes", "cursorOnly")
+MAX_SEARCH_LIMIT = 1000  # SearchQueryConfig.maxSearchLimit (query/search/SearchQueryConfig.java)
+
+
+@dataclass
+class SearchQuery(BaseQuery):
+    """SearchQuery (query/search/SearchQuery.java:52-73): which values of the search dimensions match
+    the SearchQuerySpec, and in how many rows. ``searchDimensions``: names or default dimension specs
+    (empty = every dimension of the segment, SearchStrategy.getDimsToSearch); ``query``: a
+    SearchQuerySpec JSON (a bare string is the builder's insensitive_contains; None = all); ``sort``:
+    the SearchSortSpec's StringComparator; ``limit``: 0 reads as 1000."""
+    searchDimensions: List[Any] = field(default_factory=list)
+    query: Any = None
+    sort: Any = "lexicographic"
+    limit: int = 1000
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.aggregations:
+            raise ValueError("a search query has no aggregations")
+        dims = self.searchDimensions
+        if dims is None:
+            dims = []
+        if isinstance(dims, (str, dict)):
+            dims = [dims]
+        specs = []
+        for d in dims:
+            if isinstance(d, dict):
+                if d.get("extractionFn") is not None or d.get("type", "default") not in ("default",):
+                    raise ValueError("extraction functions are out of scope")
+                specs.append((d["dimension"], d.get("outputName") or d["dimension"]))
+            else:
+                specs.append((str(d), str(d)))
+        self.dimension_specs: List[Tuple[str, str]] = specs
+        self.searchDimensions = [d for d, _ in specs]
+        q = self.query
+        if q is None:
+            q = {"type": "all"}
+        elif isinstance(q, str):
+            q = {"type": "insensitive_contains", "value": q}
+        q = dict(q)
+        if q.get("type") not in SEARCH_SPEC_TYPES:
+            raise ValueError(f"unsupported search query spec {q.get('type')!r}")
+        if q["type"] == "regex":
+            _java_regex(q["pattern"])
+        self.query = q
+        self._spec = SearchQueryDimFilter("", q)
+        self.sort = _ordering_name(self.sort.get("type") if isinstance(self.sort, dict) else self.sort)
+        if self.sort not in SEARCH_SORTS:
+            raise ValueError(f"unsupported search sort {self.sort!r}")
+        self.limit = int(self.limit)
+        if self.limit == 0:
+            self.limit = 1000
+        if self.limit < 0:
+            raise ValueError("limit must be positive")
+        st = self.context.get("searchStrategy", "useIndexes")
+        if st not in SEARCH_STRATEGIES + ("auto",):
+            raise ValueError(f"unknown searchStrategy {st!r}")
+
+    def accept(self, value: Optional[str]) -> bool:
+        """SearchQuerySpec.accept (query/search/*SearchQuerySpec.java)."""
+        return self._spec.predicate(value)
+
+    @property
+    def strategy(self) -> str:
+        """SearchStrategySelector.strategize: useIndexes (default) or cursorOnly. ``auto`` picks between
+        them with a cost model (AutoStrategy.java) that is not restated here."""
+        st = self.context.get("searchStrategy", "useIndexes")
+        if st == "auto":
+            from ._native import UnsupportedQuery
+            raise UnsupportedQuery(2, "searchStrategy auto (its cost model is not restated)")
+        return st
+
+    def _dims_json(self):
+        return [d if d == o else {"type": "default", "dimension": d, "outputName": o} for d, o in self.dimension_specs]
+
+    def to_json(self):
+        js = self._base_json("search")
+        js.pop("aggregations", None)
+        js.update({"searchDimensions": self._dims_json(), "query": dict(self.query), "sort": {"type": self.sort},
+                   "limit": self.limit})
+        return js
+
+
 def query_from_json(js: Dict[str, Any]):
     qt = js["queryType"]
     common = dict(dataSource=js.get("dataSource", "ds"), intervals=js["intervals"],
@@ -995,6 +1081,9 @@ def query_from_json(js: Dict[str, Any]):
     if qt == "groupBy":
         return GroupByQuery(dimensions=js.get("dimensions", []), limitSpec=js.get("limitSpec"),
                             having=js.get("having"), **common)
+    if qt == "search":
+        return SearchQuery(searchDimensions=js.get("searchDimensions") or [], query=js.get("query"),
+                           sort=js.get("sort") or "lexicographic", limit=int(js.get("limit", 0) or 0), **common)
     raise ValueError(f"unsupported queryType {qt!r}")
 
 

@@ -13,6 +13,10 @@ Mirrors the reference's per-segment runner + merge structure:
   per-segment grouping on the GPU, merged by dimension values (GroupByMergingQueryRunnerV2.java:170-290)
   and ordered by timestamp then dimension values.
 
+* ``SearchQueryRunnerFactory`` (query/search/SearchQueryRunnerFactory.java): per-segment hit counts from the
+  GPU (dg_search_run), the limit logic of SearchQueryRunner.run (SearchQueryRunner.java:207-260) over them,
+  merged by SearchBinaryFn (SearchBinaryFn.java:53-117).
+
 Segments that share a device are executed as ONE batched native call (all their rows in one
 launch sequence); results are still kept per segment and merged exactly like the reference merges
 per-segment runners. Cross-device / cross-rank merging is in distributed.py.
@@ -1221,6 +1225,234 @@ def postprocess_groupby(query: Q.GroupByQuery, rows: List[Q.Row]) -> List[Q.Row]
 
 
 # ----------------------------------------------------------------------------------------------
+# search
+# ----------------------------------------------------------------------------------------------
+def search_hit_key(sort: str):
+    """SearchSortSpec.getComparator (query/search/SearchSortSpec.java:50-66) as a sort key of
+    (dimension, value): the value under the sort's StringComparator, then the dimension name
+    LEXICOGRAPHIC. Hit values are never null (SearchHit: null -> "")."""
+    vk = O.sort_key(sort)
+    return lambda dim, value: (vk(value), O.lexicographic_key(dim))
+
+
+class SearchHitMap:
+    """Object2IntRBTreeMap<SearchHit> keyed by the sort's comparator: two hits the comparator calls
+    equal (NUMERIC: "1" and "1.0" of one dimension) share one entry, under the first key inserted."""
+
+    def __init__(self, sort: str):
+        self.key = search_hit_key(sort)
+        self.entries: Dict = {}  # comparator key -> [dimension, value, count]
+
+    def __len__(self):
+        return len(self.entries)
+
+    def add_to(self, dim: str, value: Optional[str], n: int):
+        value = "" if value is None else value
+        e = self.entries.setdefault(self.key(dim, value), [dim, value, 0])
+        e[2] += n
+
+    def put_all(self, other: "SearchHitMap"):
+        for k, (dim, value, n) in other.entries.items():
+            e = self.entries.get(k)
+            if e is None:
+                self.entries[k] = [dim, value, n]
+            else:
+                e[2] = n  # put: the value is replaced, the key object stays
+
+    def hits(self, limit: int) -> List[Dict]:
+        return [{"dimension": d, "value": v, "count": n}
+                for _, (d, v, n) in sorted(self.entries.items(), key=lambda kv: kv[0])][:max(limit, 0)]
+
+
+def _runner_limit(query: Q.SearchQuery) -> int:
+    """SearchThresholdAdjustingQueryRunner (SearchQueryQueryToolChest.java:353-437): a query limit at or
+    above maxSearchLimit runs its per-segment runners with maxSearchLimit."""
+    return Q.MAX_SEARCH_LIMIT if query.limit >= Q.MAX_SEARCH_LIMIT else query.limit
+
+
+def search_segment_result(query: Q.SearchQuery, timestamp: int, dims, plans, limit: int) -> Q.Result:
+    """SearchQueryRunner.run (query/search/SearchQueryRunner.java:207-260) over the engine's counts of
+    one segment. dims: per search dimension (output name, [(value, count) in dictionary id order]);
+    plans: the plan the engine took for each (N.SEARCH_PLAN_*). The execution plan is the index-only
+    executor over the bitmap dimensions, then the cursor executor over the others
+    (UseIndexesStrategy.getExecutionPlan :66-109)."""
+    def index_only(dd, lim):  # IndexOnlyExecutor.execute (UseIndexesStrategy.java:236-281)
+        ret = SearchHitMap(query.sort)
+        for name, vals in dd:
+            for value, n in vals:
+                if n > 0:
+                    ret.add_to(name, value, n)
+                    if len(ret) >= lim:
+                        return ret
+        return ret
+
+    def cursor_based(dd, lim):  # CursorBasedExecutor over the full scan's counts
+        ret = SearchHitMap(query.sort)
+        for name, vals in dd:
+            for value, n in vals:
+                if n > 0:
+                    ret.add_to(name, value, n)
+        if len(ret) >= lim:
+            # the reference stops at the row where its map reaches the limit; its counts are those of
+            # the rows up to there, which a whole-segment count cannot restate
+            raise N.UnsupportedQuery(2, f"search cursor plan reached its limit ({len(ret)} hits >= {lim})")
+        return ret
+
+    executors = []
+    for kind, fn in ((N.SEARCH_PLAN_INDEX, index_only), (N.SEARCH_PLAN_CURSOR, cursor_based)):
+        dd = [d for d, p in zip(dims, plans) if p == kind]
+        if dd:
+            executors.append((fn, dd))
+    ret = SearchHitMap(query.sort)
+    remain = limit
+    for fn, dd in executors:
+        ret.put_all(fn(dd, remain))
+        remain -= len(ret)
+    return Q.Result(timestamp, ret.hits(limit))
+
+
+def _accepted_ids(seg: GpuSegment, dim: str, query: Q.SearchQuery) -> np.ndarray:
+    """Dictionary ids of `dim` the query's SearchQuerySpec accepts (cached per segment and spec)."""
+    if seg.column_type(dim) == N.COL_MISSING:
+        return np.zeros(0, dtype=np.int32)
+    if seg.column_type(dim) != N.COL_STRING:
+        return np.zeros(1, dtype=np.int32)  # (the engine refuses the column: DG_ERR_UNSUPPORTED)
+    cache = seg.__dict__.setdefault("_search_cache", {})
+    key = (dim, repr(sorted(query.query.items(), key=lambda kv: kv[0])))
+    if key not in cache:
+        cache[key] = np.asarray([i for i, v in enumerate(seg.dictionary(dim)) if query.accept(v)], dtype=np.int32)
+    return cache[key]
+
+
+def search_dimensions(seg: GpuSegment, query: Q.SearchQuery) -> List[Tuple[str, str]]:
+    """SearchStrategy.getDimsToSearch: the query's dimension specs, or every (string) dimension of the
+    segment in its order."""
+    if query.dimension_specs:
+        return list(query.dimension_specs)
+    return [(c, c) for c in seg.columns() if c != "__time" and seg.column_type(c) == N.COL_STRING]
+
+
+def search_counts(segments: Sequence[GpuSegment], query: Q.SearchQuery, dims: Sequence[str],
+                  ids: Sequence[Sequence[np.ndarray]], stats: Optional[RunStats] = None,
+                  cancel: Optional[ctypes.c_int32] = None):
+    """One dg_search_run over segments of one device. ids[d][i]: accepted ids of dims[d] in segment i
+    (int32, ascending). Returns (counts[d][i] int64 arrays, plans[i][d])."""
+    n, nd = len(segments), len(dims)
+    scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
+    sdims = (N.dg_search_dim * max(nd, 1))()
+    total = 0
+    for d, name in enumerate(dims):
+        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in ids[d]]
+        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        cnt = np.asarray([len(a) for a in arrs], dtype=np.int32)
+        nm = name.encode("utf-8")
+        keep += [arrs, ptrs, cnt, nm]
+        sdims[d].dimension = nm
+        sdims[d].ids = ctypes.cast(ptrs, ctypes.c_void_p)
+        sdims[d].n_ids = cnt.ctypes.data
+        total += int(cnt.sum())
+    st = N.dg_search(sdims, nd, N.SEARCH_CURSOR_ONLY if query.strategy == "cursorOnly" else N.SEARCH_USE_INDEXES)
+    out = np.zeros(max(total, 1), dtype=np.int64)
+    plan = np.zeros(max(n * nd, 1), dtype=np.int32)
+    m = N.dg_metrics()
+    N.check(N.lib().dg_search_run(_handles(segments), n, ctypes.byref(scan), ctypes.byref(st), out.ctypes.data,
+                                  plan.ctypes.data, ctypes.byref(m)))
+    if stats is not None:
+        stats.add(m)
+    counts = [[None] * n for _ in range(nd)]
+    pos = 0
+    for i in range(n):
+        for d in range(nd):
+            k = len(ids[d][i])
+            counts[d][i] = out[pos:pos + k]
+            pos += k
+    return counts, plan[:n * nd].reshape(n, nd)
+
+
+def search_per_segment(segments: Sequence[GpuSegment], query: Q.SearchQuery, stats: Optional[RunStats] = None,
+                       cancel: Optional[ctypes.c_int32] = None) -> List[List[Q.Result]]:
+    """SearchQueryRunnerFactory.createRunner(segment).run for every segment (each device's segments in
+    one dg_search_run), behind the toolchest's threshold adjustment."""
+    query.strategy  # (refuses searchStrategy auto before any work)
+    limit = _runner_limit(query)
+    out: List[List[Q.Result]] = [[] for _ in segments]
+    for _, idx in _group_by_device(segments).items():
+        segs = [segments[i] for i in idx]
+        per_seg = [search_dimensions(s, query) for s in segs]
+        names: List[str] = []
+        for specs in per_seg:
+            for d, _ in specs:
+                if d not in names:
+                    names.append(d)
+        # a dimension a segment does not search (the default list of another segment) gets no ids there
+        ids = [[_accepted_ids(s, d, query) if any(d == x for x, _ in specs) else np.zeros(0, np.int32)
+                for s, specs in zip(segs, per_seg)] for d in names]
+        counts, plans = search_counts(segs, query, names, ids, stats, cancel)
+        for k, i in enumerate(idx):
+            seg = segs[k]
+            dd, pp = [], []
+            for d, o in per_seg[k]:
+                x = names.index(d)
+                if seg.column_type(d) != N.COL_STRING:
+                    continue
+                dic = seg.dictionary(d)
+                dd.append((o, [(dic[j], int(c)) for j, c in zip(ids[x][k], counts[x][k])]))
+                pp.append(int(plans[k][x]))
+            r = search_segment_result(query, seg.interval[0], dd, pp, limit)
+            out[i] = [Q.Result(r.timestamp, r.value[:query.limit])]
+    return out
+
+
+def search_binary_fn(query: Q.SearchQuery, r1: Optional[Q.Result], r2: Optional[Q.Result]) -> Optional[Q.Result]:
+    """SearchBinaryFn.apply (query/search/SearchBinaryFn.java:53-117): the two sorted hit lists merged
+    under the sort's comparator, equal (dimension, value) hits adding their counts (a hit without a
+    count makes the sum countless); the limit applies under ALL granularity only."""
+    if r1 is None:
+        return r2
+    if r2 is None:
+        return r1
+    gran = query.granularity
+    limit = query.limit if gran.is_all else -1
+    key = search_hit_key(query.sort)
+    merged = heapq.merge(r1.value, r2.value, key=lambda h: key(h["dimension"], h["value"]))
+    results: List[Dict] = []
+    prev = None
+    for hit in merged:
+        if prev is None:
+            prev = hit
+            continue
+        if prev["dimension"] == hit["dimension"] and prev["value"] == hit["value"]:
+            both = prev.get("count") is not None and hit.get("count") is not None
+            prev = {"dimension": prev["dimension"], "value": prev["value"],
+                    "count": prev["count"] + hit["count"] if both else None}
+        else:
+            results.append(prev)
+            prev = hit
+            if limit > 0 and len(results) >= limit:
+                break
+    if prev is not None and (limit < 0 or len(results) < limit):
+        results.append(prev)
+    return Q.Result(r1.timestamp if gran.is_all else gran.bucket_start(r1.timestamp), results)
+
+
+def merge_search(query: Q.SearchQuery, per_segment: List[List[Q.Result]]) -> List[Q.Result]:
+    """SearchQueryQueryToolChest.mergeResults: ResultMergeQueryRunner folds the runners' results of one
+    granularity bucket (time, then runner order) with SearchBinaryFn under the query's limit."""
+    gran = query.granularity
+    flat = sorted(((r.timestamp, si, k, r) for si, rs in enumerate(per_segment) for k, r in enumerate(rs)),
+                  key=lambda x: (x[0], x[1], x[2]))
+    merged: "OrderedDict[int, Q.Result]" = OrderedDict()
+    for ts, _, _, r in flat:
+        b = 0 if gran.is_all else gran.bucket_start(ts)
+        merged[b] = search_binary_fn(query, merged.get(b), r)
+    return [merged[b] for b in sorted(merged)]
+
+
+def run_search(segments: Sequence[GpuSegment], query: Q.SearchQuery, stats: Optional[RunStats] = None) -> List[Q.Result]:
+    return merge_search(query, search_per_segment(segments, query, stats))
+
+
+# ----------------------------------------------------------------------------------------------
 # factories (QueryRunnerFactory surface)
 # ----------------------------------------------------------------------------------------------
 def exact_granularity(query, segments: Sequence[GpuSegment]):
@@ -1366,8 +1598,19 @@ class GroupByQueryRunnerFactory(TimeseriesQueryRunnerFactory):
                 r.release()
 
 
+class SearchQueryRunnerFactory(TimeseriesQueryRunnerFactory):
+    toolchest = _ToolChest(merge_search)
+
+    @staticmethod
+    def per_segment(segments, query, stats=None):
+        return search_per_segment(segments, query, stats)
+
+    def run_merged(self, segments, query, stats=None):
+        return run_search(segments, query, stats)
+
+
 FACTORIES = {Q.TimeseriesQuery: TimeseriesQueryRunnerFactory(), Q.TopNQuery: TopNQueryRunnerFactory(),
-             Q.GroupByQuery: GroupByQueryRunnerFactory()}
+             Q.GroupByQuery: GroupByQueryRunnerFactory(), Q.SearchQuery: SearchQueryRunnerFactory()}
 
 
 def run_query(query, segments: Sequence[GpuSegment], stats: Optional[RunStats] = None):
