@@ -4404,7 +4404,36 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   };
   bool rows_elems = !any_multi && !has_float_sum(plan) && !env_on("DG_GB_COUNT");
   for (int i = 0; i < n && rows_elems; ++i) rows_elems = !cur[i].any || all_rows_in(i);
-  launch_gb_keygen(d_jobs, d_tile, ntiles, &sb, plan, st, any_multi, rows_elems ? total : -1);
+  // The keygen fused into the first radix pass (launch_gb_sort_generated): the sort grouper over a
+  // rows_elems call in row-ref mode with packed words, no time view (the bucket would need __time),
+  // every dimension a single-value little-endian id view or missing, and the payload columns decoded
+  // in place — the keygen would only write the sort words. A segment whose payload is not all in place
+  // (a literal-only LZ4 block, as a one-row segment's, is viewed rather than decoded) keeps the keygen
+  // over its own tiles for the payload records alone; when such segments hold more than a quarter of
+  // the rows the keygen runs as ever (it reads their ids anyway: generating them again saves little).
+  // DG_NO_FUSED_KEYGEN=1: the keygen runs (same-box A/B and tests). A time-bucketed groupBy keeps it.
+  bool fused_keygen = rows_elems && !use_hash && ntiles > 0 && radix_sort_generates(&sb, key_bits, total) &&
+                      !env_on("DG_NO_FUSED_KEYGEN");
+  const uint32_t all_inplace = na >= 32 ? 0xFFFFFFFFu : (1u << na) - 1u;
+  int64_t keygen_rows = 0;  // rows of the segments whose payload the keygen writes
+  for (int i = 0; i < n && fused_keygen; ++i) {
+    if (!cur[i].any) continue;
+    const GbJob& j = gj[i];
+    fused_keygen = j.time.kind == VIEW_ABSENT;
+    if (j.inplace != all_inplace) keygen_rows += rows[i];
+    for (int d = 0; d < nd && fused_keygen; ++d)
+      fused_keygen = j.moff[d].kind == VIEW_ABSENT &&
+                     (j.dims[d].kind == VIEW_ABSENT || (j.dims[d].kind == VIEW_IDS && !(j.dims[d].pad & kViewBigEndian) &&
+                                                        j.dims[d].log2_per >= kRsGenMinBlockLog2));
+  }
+  fused_keygen = fused_keygen && keygen_rows * 4 <= total;
+  if (!fused_keygen) {
+    launch_gb_keygen(d_jobs, d_tile, ntiles, &sb, plan, st, any_multi, rows_elems ? total : -1);
+  } else if (keygen_rows > 0) {
+    for (int i = 0; i < n; ++i)
+      if (cur[i].any && gj[i].inplace != all_inplace)
+        launch_gb_keygen_payload(d_jobs, d_tile, gj[i].tile_begin, (int)((rows[i] + kTileRows - 1) / kTileRows), &sb, plan, st);
+  }
   phase_event(ctx->ev[5], st);
   // The hash grouper: the elements aggregated into the HBM table (per tile in LDS first), then one
   // read-back of the group count, which sizes the group sort and the result (cap = groups). In
@@ -4425,7 +4454,8 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
                        (long long)tab.max_groups, (long long)tab.capacity);
     if (rc) return rc;
   } else {
-    launch_radix_sort(&sb, key_bits, st);
+    if (fused_keygen) launch_gb_sort_generated(d_jobs, n, total, &sb, key_bits, st);
+    else launch_radix_sort(&sb, key_bits, st);
     phase_event(ctx->ev[6], st);
   }
   DG_CHECK_INTERRUPT(intr);
@@ -4536,7 +4566,7 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   m.decode_ms = f2;
   decode_metrics(db, db_side, &m, ctx->ev[0]);
   m.aggregate_ms = f3;
-  m.keygen_ms = f4;
+  m.keygen_ms = fused_keygen ? 0.0 : f4;  // exactly 0: no keygen ran (the first sort pass formed the words)
   m.sort_ms = f5;
   m.reduce_ms = f6;  // includes the wait for the side-stream payload decode
   if (reduce_timed) {

@@ -731,6 +731,23 @@ void launch_gb_keygen(const GbJob* d_jobs, const int32_t* d_tile_job, int ntiles
                       hipStream_t s, bool multi = false, int64_t all_rows = -1);
 // stable LSD radix sort of sb->keys/refs[cur] on key bits [0, key_bits)
 void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s);
+// The keygen fused into the first radix pass: for a call whose every row is an element in row order
+// (launch_gb_keygen's all_rows case) with no time view, single-value little-endian id views (or
+// missing dimensions) and every payload column decoded in place, the sort word of element e is a
+// function of e and the job table alone. launch_gb_sort_generated sets sb->n[0] = rows and sorts as
+// launch_radix_sort does, its first pass (and that pass's digit totals) forming the words in
+// registers from the id columns: no k_gb_keygen launch, no write and two reads of the words less.
+// A job with a payload column the decoder did not write in place (a literal-only LZ4 block is viewed,
+// not decoded) still needs its payload records: launch_gb_keygen_payload runs k_gb_keygen over that
+// job's tiles [tile0, tile0 + ntiles) for the payload alone (an all_rows, row-ref call).
+// radix_sort_generates: what the sort itself needs for it (packed words by row ref, at least one pass).
+// Every id view of such a call holds at least 2^kRsGenMinBlockLog2 rows per block (64-KiB blocks of
+// ids of at most 4 bytes hold 2^14), so a wave's share of a sort tile spans two blocks at the most.
+constexpr int kRsGenMinBlockLog2 = 13;
+bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows);
+void launch_gb_keygen_payload(const GbJob* d_jobs, const int32_t* d_tile_job, int tile0, int ntiles, SortBufs* sb,
+                              AggPlan plan, hipStream_t s);
+void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s);
 // run heads of the sorted keys: sb->run_cnt = per-tile offsets, sb->n[1] = runs
 void launch_run_heads(SortBufs* sb, hipStream_t s);
 // head_pos[g] = first sorted element of run g (after launch_run_heads)

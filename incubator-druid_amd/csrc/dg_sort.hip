@@ -29,6 +29,7 @@
 // row loop (within the 1e-9 relative tolerance north_star states).
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <type_traits>
 
 #include "dg_device.h"
 
@@ -135,19 +136,116 @@ __device__ __forceinline__ bool gb_select(const GbJob& j, int64_t r, int64_t* bu
   return true;
 }
 
+// The parts of a single-value key, shared by k_gb_keygen and the radix sort's generated first pass
+// (rs_gen_words): the fields above the dimensions, a dimension's field, and the packed sort word.
+__device__ __forceinline__ uint64_t gb_key_base(const GbJob& j, int64_t bucket) {
+  return ((uint64_t)j.seg_slot << j.seg_shift) | ((uint64_t)bucket << j.bucket_shift);
+}
+
+// dimension d's field of a row whose dictionary id is `id` (a missing dimension: every row has the null value)
+__device__ __forceinline__ uint64_t gb_dim_field(const GbJob& j, int d, uint32_t id) {
+  uint32_t g;
+  if (j.dims[d].kind == VIEW_IDS) g = j.remap[d] ? (uint32_t)j.remap[d][id] : id;
+  else g = (uint32_t)j.null_gid[d];
+  return (uint64_t)g << j.dim_shift[d];
+}
+
+// packed element: [key | reference in the low kshift bits]
+__device__ __forceinline__ uint64_t gb_pack(uint64_t key, int kshift, uint32_t ref) { return (key << kshift) | ref; }
+
 __device__ __forceinline__ uint64_t gb_key(const GbJob& j, int64_t r, int64_t bucket) {
-  uint64_t k = ((uint64_t)j.seg_slot << j.seg_shift) | ((uint64_t)bucket << j.bucket_shift);
-  for (int d = 0; d < j.ndims; ++d) {
-    uint32_t g;
-    if (j.dims[d].kind == VIEW_IDS) {
-      const uint32_t id = load_id(j.dims[d], r);
-      g = j.remap[d] ? (uint32_t)j.remap[d][id] : id;
-    } else {
-      g = (uint32_t)j.null_gid[d];  // missing dimension: every row has the null value
-    }
-    k |= (uint64_t)g << j.dim_shift[d];
-  }
+  uint64_t k = gb_key_base(j, bucket);
+  for (int d = 0; d < j.ndims; ++d) k |= gb_dim_field(j, d, j.dims[d].kind == VIEW_IDS ? load_id(j.dims[d], r) : 0u);
   return k;
+}
+
+// little-endian dictionary id `row` of a block of W-byte ids (bp = the block's first id). A 3-byte id
+// is two aligned dword loads (the slot / flat allocation extends past the last id's dword)
+template <int W>
+__device__ __forceinline__ uint32_t gb_block_id(const uint8_t* bp, uint32_t row) {
+  const uint32_t off = row * (uint32_t)W;
+  if (W == 3) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(bp + (off & ~3u));
+    return __builtin_amdgcn_alignbyte(w[1], w[0], off & 3u) & 0xFFFFFFu;
+  }
+  if (W == 1) return bp[off];
+  if (W == 2) return *reinterpret_cast<const uint16_t*>(bp + off);
+  return *reinterpret_cast<const uint32_t*>(bp + off);
+}
+
+// Keys of a batch of kB rows per thread of one job whose dimension views are little-endian ids: each
+// dimension's id loads of the batch in flight together, then its dictionary-map lookups together
+// (the id width and the map's presence are decided once per batch, outside the unrolled loads: a
+// branch per load left them waiting for one another).
+// `rows` names the batch: row(u) = the thread's u-th row, always one of the batch's rows (a thread
+// with no u-th row names another one and ignores that key), and blocks(v) = the (at most two) blocks
+// of view v that the batch's rows lie in, as {first block's index, its pointer, the other block's pointer}.
+// `need`: the key bits the caller looks at; a dimension whose field has none of them is not read.
+struct GbBlocks {
+  int64_t ba;
+  const uint8_t* pa;
+  const uint8_t* pb;
+};
+template <int kB, class Rows>
+__device__ __forceinline__ void gb_batch_keys(const GbJob& j, int64_t bucket, const Rows& rows, uint64_t* key,
+                                              uint64_t need = ~0ull) {
+#pragma unroll
+  for (int u = 0; u < kB; ++u) key[u] = gb_key_base(j, bucket);
+  auto needed = [&](int d) {
+    const uint64_t field = (j.dim_bits[d] >= 64 ? 0ull : 1ull << j.dim_bits[d]) - 1ull;
+    return ((field << j.dim_shift[d]) & need) != 0;
+  };
+  // dimension d's ids of the batch, then their merged ids
+  auto load_ids = [&](int d, uint32_t* id) {
+    const ColView& v = j.dims[d];
+#pragma unroll
+    for (int u = 0; u < kB; ++u) id[u] = 0;
+    if (v.kind != VIEW_IDS || !needed(d)) return;
+    const GbBlocks b = rows.blocks(v);
+    const int log2_per = v.log2_per;
+    const int64_t in_block = ((int64_t)1 << log2_per) - 1;
+    auto load_w = [&](auto w) {
+#pragma unroll
+      for (int u = 0; u < kB; ++u) {
+        const int64_t r = rows.row(u);
+        id[u] = gb_block_id<decltype(w)::value>((r >> log2_per) == b.ba ? b.pa : b.pb, (uint32_t)(r & in_block));
+      }
+    };
+    switch (v.width) {
+      case 1: load_w(std::integral_constant<int, 1>()); break;
+      case 2: load_w(std::integral_constant<int, 2>()); break;
+      case 3: load_w(std::integral_constant<int, 3>()); break;
+      default: load_w(std::integral_constant<int, 4>()); break;
+    }
+  };
+  auto merge_ids = [&](int d, const uint32_t* id) {
+    const int32_t* rm = j.remap[d];
+    const int sh = j.dim_shift[d];
+    if (!needed(d)) return;
+    if (j.dims[d].kind != VIEW_IDS) {  // missing dimension: every row has the null value
+#pragma unroll
+      for (int u = 0; u < kB; ++u) key[u] |= (uint64_t)(uint32_t)j.null_gid[d] << sh;
+    } else if (rm) {
+#pragma unroll
+      for (int u = 0; u < kB; ++u) key[u] |= (uint64_t)(uint32_t)rm[id[u]] << sh;
+    } else {
+#pragma unroll
+      for (int u = 0; u < kB; ++u) key[u] |= (uint64_t)id[u] << sh;
+    }
+  };
+  if (j.ndims == 2) {  // (the common two-dimension key: both columns' loads in flight, then both maps)
+    uint32_t id0[kB], id1[kB];
+    load_ids(0, id0);
+    load_ids(1, id1);
+    merge_ids(0, id0);
+    merge_ids(1, id1);
+  } else {
+    for (int d = 0; d < j.ndims; ++d) {
+      uint32_t id[kB];
+      load_ids(d, id);
+      merge_ids(d, id);
+    }
+  }
 }
 
 // Multi-value dimensions: a row groups under every combination of its dimensions' values (an empty
@@ -258,24 +356,28 @@ template <bool MULTI>
 __global__ __launch_bounds__(256) void k_gb_keygen(const GbJob* __restrict__ jobs, const int32_t* __restrict__ tile_job,
                                                    const uint32_t* __restrict__ offs, uint64_t* __restrict__ keys,
                                                    uint32_t* __restrict__ refs, int kshift, AggPlan plan,
-                                                   uint64_t* __restrict__ payload, int pw, int rowref, int rows_elems) {
+                                                   uint64_t* __restrict__ payload, int pw, int rowref, int rows_elems,
+                                                   int tile0) {
   __shared__ uint32_t s_tmp[4];
-  const GbJob& j = jobs[tile_job[blockIdx.x]];
-  const int64_t r0 = (int64_t)(blockIdx.x - j.tile_begin) * kTileRows;
+  const int tile = (int)blockIdx.x + tile0;  // (tile0: the launch covers the tiles from there, one job's)
+  const GbJob& j = jobs[tile_job[tile]];
+  const int64_t r0 = (int64_t)(tile - j.tile_begin) * kTileRows;
   const int64_t r1 = min((int64_t)j.nrows, r0 + kTileRows);
   // rows_elems: every row of the call is an element, in row order (no filter, every row's time inside
   // the interval, one element per row): the tile's first element is its first row's index over the
   // call, no count pass
-  uint32_t base = rows_elems ? j.row_base + (uint32_t)r0 : offs[blockIdx.x];
+  uint32_t base = rows_elems ? j.row_base + (uint32_t)r0 : offs[tile];
   const uint32_t inplace = rowref ? j.inplace : 0u;
   const bool all_inplace = pw > 0 && inplace == (pw >= 32 ? 0xFFFFFFFFu : (1u << pw) - 1u);
-  // the element's sort word(s) and payload record
+  // the element's sort word(s) and payload record (keys null: the payload only — the first radix pass
+  // generates the words, launch_gb_keygen_payload)
   auto emit = [&](uint32_t idx, uint32_t ref, uint64_t key, auto&& val) {
-    if (refs) {
+    if (!keys) {
+    } else if (refs) {
       keys[idx] = key;
       refs[idx] = ref;
     } else {
-      keys[idx] = (key << kshift) | ref;
+      keys[idx] = gb_pack(key, kshift, ref);
     }
     if (all_inplace) return;
     if (pw == 2 && !inplace) {
@@ -307,61 +409,20 @@ __global__ __launch_bounds__(256) void k_gb_keygen(const GbJob* __restrict__ job
       direct &= ((inplace >> a) & 1u) || j.vals[a].kind == VIEW_ABSENT ||
                 (r0 >> j.vals[a].log2_per) == ((r1 - 1) >> j.vals[a].log2_per);
     if (direct) {
-      // kB rows per thread (one batch: the whole tile), each dimension's id loads of the batch in flight
-      // together, then its dictionary-map lookups together
+      // kB rows per thread (one batch: the whole tile, inside one block of every view)
       constexpr int kB = kTileRows / 256;
       static_assert(kTileRows % 256 == 0, "whole batches per tile");
+      struct TileRows {
+        int64_t r0, r1;
+        __device__ __forceinline__ int64_t row(int u) const { return min(r0 + threadIdx.x + 256 * u, r1 - 1); }
+        __device__ __forceinline__ GbBlocks blocks(const ColView& v) const {
+          const int64_t blk = r0 >> v.log2_per;
+          const uint8_t* bp = v.blocks[blk];
+          return GbBlocks{blk, bp, bp};
+        }
+      };
       uint64_t key[kB];
-#pragma unroll
-      for (int u = 0; u < kB; ++u) key[u] = ((uint64_t)j.seg_slot << j.seg_shift) | ((uint64_t)tbucket << j.bucket_shift);
-      // dimension d's ids of the batch, then their merged ids (rows past r1: id 0, a valid index)
-      auto load_ids = [&](int d, uint32_t* id) {
-        const ColView& v = j.dims[d];
-        if (v.kind != VIEW_IDS) return;
-        const int64_t blk = r0 >> v.log2_per;
-        const uint8_t* bp = v.blocks[blk];
-#pragma unroll
-        for (int u = 0; u < kB; ++u) {
-          const int64_t r = r0 + threadIdx.x + 256 * u;
-          id[u] = 0;
-          if (r < r1) {
-            const uint32_t off = (uint32_t)(r - (blk << v.log2_per)) * (uint32_t)v.width;
-            if (v.width == 3) {  // the slot / flat allocation extends past the last id's dword
-              const uint32_t* w = reinterpret_cast<const uint32_t*>(bp + (off & ~3u));
-              id[u] = __builtin_amdgcn_alignbyte(w[1], w[0], off & 3u) & 0xFFFFFFu;
-            } else if (v.width == 1) {
-              id[u] = bp[off];
-            } else if (v.width == 2) {
-              id[u] = *reinterpret_cast<const uint16_t*>(bp + off);
-            } else {
-              id[u] = *reinterpret_cast<const uint32_t*>(bp + off);
-            }
-          }
-        }
-      };
-      auto merge_ids = [&](int d, uint32_t* id) {
-        const int32_t* rm = j.remap[d];
-        if (j.dims[d].kind != VIEW_IDS) {
-#pragma unroll
-          for (int u = 0; u < kB; ++u) key[u] |= (uint64_t)(uint32_t)j.null_gid[d] << j.dim_shift[d];
-          return;
-        }
-#pragma unroll
-        for (int u = 0; u < kB; ++u) key[u] |= (uint64_t)(rm ? (uint32_t)rm[id[u]] : id[u]) << j.dim_shift[d];
-      };
-      if (j.ndims == 2) {  // (the common two-dimension key: both columns' loads in flight, then both maps)
-        uint32_t id0[kB], id1[kB];
-        load_ids(0, id0);
-        load_ids(1, id1);
-        merge_ids(0, id0);
-        merge_ids(1, id1);
-      } else {
-        for (int d = 0; d < j.ndims; ++d) {
-          uint32_t id[kB];
-          load_ids(d, id);
-          merge_ids(d, id);
-        }
-      }
+      gb_batch_keys<kB>(j, tbucket, TileRows{r0, r1}, key);
 #pragma unroll
       for (int u = 0; u < kB; ++u) {
         const int64_t r = r0 + threadIdx.x + 256 * u;
@@ -430,11 +491,18 @@ void launch_gb_keygen(const GbJob* d_jobs, const int32_t* d_tile_job, int ntiles
   }
   if (multi)
     hipLaunchKernelGGL(k_gb_keygen<true>, dim3(ntiles), dim3(256), 0, s, d_jobs, d_tile_job, sb->tile_cnt,
-                       sb->keys[sb->cur], sb->refs[sb->cur], sb->ref_bits, plan, sb->payload, sb->pw, 0, 0);
+                       sb->keys[sb->cur], sb->refs[sb->cur], sb->ref_bits, plan, sb->payload, sb->pw, 0, 0, 0);
   else
     hipLaunchKernelGGL(k_gb_keygen<false>, dim3(ntiles), dim3(256), 0, s, d_jobs, d_tile_job, sb->tile_cnt,
                        sb->keys[sb->cur], sb->refs[sb->cur], sb->ref_bits, plan, sb->payload, sb->pw, sb->row_refs,
-                       rows_elems ? 1 : 0);
+                       rows_elems ? 1 : 0, 0);
+}
+
+void launch_gb_keygen_payload(const GbJob* d_jobs, const int32_t* d_tile_job, int tile0, int ntiles, SortBufs* sb,
+                              AggPlan plan, hipStream_t s) {
+  if (ntiles <= 0) return;
+  hipLaunchKernelGGL(k_gb_keygen<false>, dim3(ntiles), dim3(256), 0, s, d_jobs, d_tile_job, sb->tile_cnt, nullptr, nullptr,
+                     sb->ref_bits, plan, sb->payload, sb->pw, sb->row_refs, 1, tile0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -459,27 +527,129 @@ constexpr uint64_t kLbAgg = Lb<uint64_t>::kAgg;  // (the groupBy reduce's per-ti
 constexpr uint64_t kLbPre = Lb<uint64_t>::kPre;
 constexpr uint64_t kLbVal = Lb<uint64_t>::kVal;
 
+// Where the first pass's elements come from. kSrcWords: the sort words the keygen (or another
+// producer) wrote. kSrcGen: generated in registers from the call's GbJob table — a call whose every
+// row is an element in row order (the keygen's rows_elems, packed words, no time view, single-value
+// little-endian id views, payload decoded in place): element e is row e - row_base of the job with
+// row_base <= e < row_base + nrows, and its word is gb_pack(key of that row, kshift, e). The keygen's
+// write of the words and the first pass's reads of them are then not needed.
+constexpr int kSrcWords = 0, kSrcGen = 1;
+// chunks of a wave's share generated together (A/B builds): the scatter keeps its four waves per SIMD
+// at 4 (at 8 and 16 it needs 156 and 249 registers); the digit totals have the registers for 8
+#ifndef DG_RS_GEN_BATCH
+#define DG_RS_GEN_BATCH 4
+#endif
+#ifndef DG_RS_GEN_BATCH_HIST
+#define DG_RS_GEN_BATCH_HIST 8
+#endif
+struct RsGen {
+  const GbJob* jobs;
+  int njobs;
+  int kshift;  // the words' reference bits
+};
+
+// job of element e: the last one whose row_base <= e (bases ascend; a job without rows shares its
+// base with the next one, and none follows the last job with rows at a base <= e < n)
+__device__ __forceinline__ int rs_gen_job(const RsGen& g, uint32_t e) {
+  int lo = 0, hi = g.njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (g.jobs[mid].row_base <= e) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The generated words of one wave's share of a tile: NC chunks of 64 consecutive elements from e_wave
+// (wave-uniform), chunk c's lane l holding element e_wave + 64 c + l; elements at or past e_end get 0.
+// The share's rows of a job are one batch of the keygen's batch path (gb_batch_keys): the job and each
+// view's block pointers are wave-uniform, NC id loads per dimension in flight. A share is not aligned
+// to segments or column blocks: it may hold rows of several jobs, and a job's rows in it may lie in
+// two neighbouring blocks of a view (kRsGenMinBlockLog2: never more).
+// `need`: the word bits the caller looks at (the digit totals: one digit); the others may be missing.
+template <int NC, int G>
+__device__ __forceinline__ void rs_gen_words(const RsGen& g, uint32_t e_wave, uint32_t e_end, int lane, uint64_t* k,
+                                             uint64_t need = ~0ull) {
+  static_assert(NC * 64 <= (1 << kRsGenMinBlockLog2), "a share spans at most two blocks of a view");
+  // (both are the same in every lane; said so, the job search and the block pointers are scalar work)
+  e_wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)e_wave);
+  e_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)e_end);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) k[c] = 0;
+  if (e_wave >= e_end) return;
+  const uint32_t e_last = min(e_end, e_wave + (uint32_t)(NC * 64)) - 1u;
+  // one batch per job with rows in the share (one job, but for the few shares that straddle a segment boundary)
+  for (int ji = rs_gen_job(g, e_wave), jl = rs_gen_job(g, e_last); ji <= jl; ++ji) {
+    const GbJob& j = g.jobs[ji];
+    if (j.nrows <= 0) continue;
+    const uint32_t lo = max(e_wave, j.row_base), hi = min(e_last, j.row_base + (uint32_t)j.nrows - 1u);
+    if (lo > hi) continue;
+    // G chunks at a time
+    struct ShareRows {
+      int64_t r_first;     // the job's row of the batch's first element (negative: the job starts inside the share)
+      int64_t r_lo, r_hi;  // the share's first and last row of the job
+      int lane;
+      __device__ __forceinline__ int64_t row(int u) const { return min(max(r_first + 64 * u + lane, r_lo), r_hi); }
+      __device__ __forceinline__ GbBlocks blocks(const ColView& v) const {
+        const int64_t ba = r_lo >> v.log2_per;
+        return GbBlocks{ba, v.blocks[ba], v.blocks[r_hi >> v.log2_per]};
+      }
+    };
+    constexpr int kG = NC < G ? NC : G;
+    static_assert(NC % kG == 0, "whole batches per share");
+#pragma unroll
+    for (int c0 = 0; c0 < NC; c0 += kG) {
+      if (e_wave + (uint32_t)(64 * c0) > hi || e_wave + (uint32_t)(64 * (c0 + kG) - 1) < lo) continue;  // (none of the job's rows)
+      uint64_t key[kG];
+      gb_batch_keys<kG>(j, 0, ShareRows{(int64_t)e_wave + 64 * c0 - (int64_t)j.row_base, (int64_t)(lo - j.row_base),
+                                        (int64_t)(hi - j.row_base), lane}, key, need >> g.kshift);
+#pragma unroll
+      for (int c = 0; c < kG; ++c) {
+        const uint32_t e = e_wave + (uint32_t)(64 * (c0 + c) + lane);
+        if (e >= lo && e <= hi) k[c0 + c] = gb_pack(key[c], g.kshift, e);
+      }
+    }
+  }
+}
+
 // the first pass's digit totals: totals[d] += elements whose digit (bits above shift) is d
+template <int SRC>
 __global__ __launch_bounds__(kST) void k_rs_hist0(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ n_ptr,
-                                                  int shift, int bits, uint32_t* __restrict__ totals) {
+                                                  int shift, int bits, uint32_t* __restrict__ totals, RsGen gen) {
   __shared__ uint32_t s_h[4][kMaxBins];  // one histogram per wave (fewer same-address LDS atomics)
   const int tid = threadIdx.x, wave = tid >> 6;
   for (int i = tid; i < 4 * kMaxBins; i += kST) (&s_h[0][0])[i] = 0;
   __syncthreads();
   const uint32_t n = *n_ptr;
   const uint64_t mask = (1ull << bits) - 1;
-  // four independent loads in flight per thread (one per iteration left the read latency-bound)
-  constexpr int kU = 4;
-  const int64_t stride = (int64_t)gridDim.x * kST;
-  int64_t i = (int64_t)blockIdx.x * kST + tid;
-  for (; i + (kU - 1) * stride < (int64_t)n; i += kU * stride) {
-    uint64_t w[kU];
+  if (SRC == kSrcGen) {
+    // whole sort tiles per workgroup, a wave's share generated like the scatter's (same grid: each
+    // workgroup strides over the tiles and flushes its histogram once)
+    constexpr int kNC = kSortTile / kST;
+    const uint32_t wbase = (uint32_t)wave * (uint32_t)(kNC * 64);
+    for (int64_t base = (int64_t)blockIdx.x * kSortTile; base < (int64_t)n; base += (int64_t)gridDim.x * kSortTile) {
+      const uint32_t e_end = (uint32_t)min<int64_t>((int64_t)n, base + kSortTile);
+      const uint32_t e_wave = (uint32_t)base + wbase;
+      uint64_t w[kNC];
+      rs_gen_words<kNC, DG_RS_GEN_BATCH_HIST>(gen, e_wave, e_end, tid & 63, w, mask << shift);  // (only the dimensions under the digit)
 #pragma unroll
-    for (int u = 0; u < kU; ++u) w[u] = keys[i + u * stride];
+      for (int c = 0; c < kNC; ++c)
+        if (e_wave + (uint32_t)(64 * c + (tid & 63)) < e_end) atomicAdd(&s_h[wave][(int)((w[c] >> shift) & mask)], 1u);
+    }
+  } else {
+    // four independent loads in flight per thread (one per iteration left the read latency-bound)
+    constexpr int kU = 4;
+    const int64_t stride = (int64_t)gridDim.x * kST;
+    int64_t i = (int64_t)blockIdx.x * kST + tid;
+    for (; i + (kU - 1) * stride < (int64_t)n; i += kU * stride) {
+      uint64_t w[kU];
 #pragma unroll
-    for (int u = 0; u < kU; ++u) atomicAdd(&s_h[wave][(int)((w[u] >> shift) & mask)], 1u);
+      for (int u = 0; u < kU; ++u) w[u] = keys[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) atomicAdd(&s_h[wave][(int)((w[u] >> shift) & mask)], 1u);
+    }
+    for (; i < (int64_t)n; i += stride) atomicAdd(&s_h[wave][(int)((keys[i] >> shift) & mask)], 1u);
   }
-  for (; i < (int64_t)n; i += stride) atomicAdd(&s_h[wave][(int)((keys[i] >> shift) & mask)], 1u);
   __syncthreads();
   for (int d = tid; d < (1 << bits); d += kST) {
     const uint32_t c = s_h[0][d] + s_h[1][d] + s_h[2][d] + s_h[3][d];
@@ -509,13 +679,16 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
 // earlier tiles' counts walking back until one has published its inclusive prefix, and publishes its
 // own. The tile is then reordered by digit in LDS, so the global stores of a wave run along each
 // digit's contiguous output range (coalesced) instead of scattering lane by lane.
-template <bool REFS, class W>
+// SRC = kSrcGen (the first pass of an eligible groupBy): the tile's elements are generated from the
+// job table (rs_gen_words) instead of read from kin; everything after the load is the same code.
+template <bool REFS, class W, int SRC>
 __global__ __launch_bounds__(kRsT) void k_rs_scatter(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                     uint64_t* __restrict__ kout, uint32_t* __restrict__ vout,
                                                     const uint32_t* __restrict__ n_ptr, int shift, int bits,
                                                     const uint32_t* __restrict__ totals, W* __restrict__ status,
                                                     uint32_t* __restrict__ tile_ctr, int nshift, int nbits,
-                                                    uint32_t* __restrict__ ntotals) {
+                                                    uint32_t* __restrict__ ntotals, RsGen gen) {
+  static_assert(SRC == kSrcWords || !REFS, "generated elements are packed words");
   __shared__ uint64_t s_k[kRsTile];
   __shared__ uint32_t s_v[REFS ? kRsTile : 1];
   __shared__ uint32_t s_cnt[kRsW * kMaxBins];
@@ -546,12 +719,16 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const uint64_t* __restrict_
   const int wbase = wave * (kRsTile / kRsW);
   uint64_t k[kRsSPT];
   uint32_t v[kRsSPT], rank[kRsSPT];
+  if (SRC == kSrcGen) {
+    rs_gen_words<kRsSPT, DG_RS_GEN_BATCH>(gen, (uint32_t)base + (uint32_t)wbase, (uint32_t)base + (uint32_t)tile_n, lane, k);
+  } else {
 #pragma unroll
-  for (int c = 0; c < kRsSPT; ++c) {
-    const int x = wbase + c * 64 + lane;
-    const bool ok = x < tile_n;
-    k[c] = ok ? kin[base + x] : 0ull;
-    if (REFS) v[c] = ok ? vin[base + x] : 0u;
+    for (int c = 0; c < kRsSPT; ++c) {
+      const int x = wbase + c * 64 + lane;
+      const bool ok = x < tile_n;
+      k[c] = ok ? kin[base + x] : 0ull;
+      if (REFS) v[c] = ok ? vin[base + x] : 0u;
+    }
   }
   uint32_t* cnt = s_cnt + wave * kMaxBins;
   uint64_t* peer = s_peer + wave * kMaxBins;
@@ -688,8 +865,10 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const uint64_t* __restrict_
   }
 }
 
-// LSD passes over key bits [lo, hi) of the key field (above the element index bits)
-static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s) {
+// LSD passes over key bits [lo, hi) of the key field (above the element index bits). gen: the first
+// pass and its digit totals generate their elements from the job table (nothing has written
+// sb->keys[sb->cur]); the later passes read what the pass before them stored, as always.
+static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGen* gen) {
   const int kb = hi - lo;
   if (kb <= 0) return;
   const int npass = (kb + kMaxDigitBits - 1) / kMaxDigitBits;
@@ -698,10 +877,15 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s) {
   uint32_t* totals = sb->bin_total;                            // [npass][kMaxBins]
   uint32_t* ctr = sb->bin_total + kRsMaxPasses * kMaxBins;     // [npass] tile counters
   if (!zero_async(sb->bin_total, ((size_t)kRsMaxPasses * kMaxBins + kRsMaxPasses) * sizeof(uint32_t), s)) return;
-  // the first pass's digit totals from one read of the keys; every pass's scatter counts the next
-  // pass's digits of the keys it stores
-  hipLaunchKernelGGL(k_rs_hist0, dim3(std::min(nt, 4096)), dim3(kST), 0, s, sb->keys[sb->cur], sb->n,
-                     sb->ref_bits + lo, std::min(kb, w), totals);
+  const RsGen none{nullptr, 0, 0};
+  // the first pass's digit totals from one read of the keys (gen: of the ids); every pass's scatter
+  // counts the next pass's digits of the keys it stores
+  if (gen)
+    hipLaunchKernelGGL(k_rs_hist0<kSrcGen>, dim3(std::min(nt, 4096)), dim3(kST), 0, s, nullptr, sb->n, sb->ref_bits + lo,
+                       std::min(kb, w), totals, *gen);
+  else
+    hipLaunchKernelGGL(k_rs_hist0<kSrcWords>, dim3(std::min(nt, 4096)), dim3(kST), 0, s, sb->keys[sb->cur], sb->n,
+                       sb->ref_bits + lo, std::min(kb, w), totals, none);
   for (int p = 0, off = lo; p < npass; ++p, off += w) {
     const int bits = std::min(w, hi - off);
     const int shift = sb->ref_bits + off;
@@ -715,18 +899,24 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s) {
     uint32_t* st32 = reinterpret_cast<uint32_t*>(sb->lb_status);
     uint64_t* st64 = sb->lb_status;
     const uint32_t* tp = totals + (size_t)p * kMaxBins;
-    if (sb->refs[in] && narrow)
-      hipLaunchKernelGGL((k_rs_scatter<true, uint32_t>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], sb->refs[in], sb->keys[out],
-                         sb->refs[out], sb->n, shift, bits, tp, st32, ctr + p, shift + w, nbits, nt_tot);
+    if (gen && p == 0 && narrow)
+      hipLaunchKernelGGL((k_rs_scatter<false, uint32_t, kSrcGen>), dim3(nt), dim3(kRsT), 0, s, nullptr, nullptr, sb->keys[out],
+                         nullptr, sb->n, shift, bits, tp, st32, ctr + p, shift + w, nbits, nt_tot, *gen);
+    else if (gen && p == 0)
+      hipLaunchKernelGGL((k_rs_scatter<false, uint64_t, kSrcGen>), dim3(nt), dim3(kRsT), 0, s, nullptr, nullptr, sb->keys[out],
+                         nullptr, sb->n, shift, bits, tp, st64, ctr + p, shift + w, nbits, nt_tot, *gen);
+    else if (sb->refs[in] && narrow)
+      hipLaunchKernelGGL((k_rs_scatter<true, uint32_t, kSrcWords>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], sb->refs[in],
+                         sb->keys[out], sb->refs[out], sb->n, shift, bits, tp, st32, ctr + p, shift + w, nbits, nt_tot, none);
     else if (sb->refs[in])
-      hipLaunchKernelGGL((k_rs_scatter<true, uint64_t>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], sb->refs[in], sb->keys[out],
-                         sb->refs[out], sb->n, shift, bits, tp, st64, ctr + p, shift + w, nbits, nt_tot);
+      hipLaunchKernelGGL((k_rs_scatter<true, uint64_t, kSrcWords>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], sb->refs[in],
+                         sb->keys[out], sb->refs[out], sb->n, shift, bits, tp, st64, ctr + p, shift + w, nbits, nt_tot, none);
     else if (narrow)
-      hipLaunchKernelGGL((k_rs_scatter<false, uint32_t>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], nullptr, sb->keys[out],
-                         nullptr, sb->n, shift, bits, tp, st32, ctr + p, shift + w, nbits, nt_tot);
+      hipLaunchKernelGGL((k_rs_scatter<false, uint32_t, kSrcWords>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], nullptr,
+                         sb->keys[out], nullptr, sb->n, shift, bits, tp, st32, ctr + p, shift + w, nbits, nt_tot, none);
     else
-      hipLaunchKernelGGL((k_rs_scatter<false, uint64_t>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], nullptr, sb->keys[out],
-                         nullptr, sb->n, shift, bits, tp, st64, ctr + p, shift + w, nbits, nt_tot);
+      hipLaunchKernelGGL((k_rs_scatter<false, uint64_t, kSrcWords>), dim3(nt), dim3(kRsT), 0, s, sb->keys[in], nullptr,
+                         sb->keys[out], nullptr, sb->n, shift, bits, tp, st64, ctr + p, shift + w, nbits, nt_tot, none);
     sb->cur = out;
   }
 }
@@ -734,7 +924,22 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s) {
 void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s) {
   if (key_bits <= 0) return;
   static_assert(64 / kMaxDigitBits <= kRsMaxPasses, "passes of a 64-bit key");
-  radix_passes(sb, 0, key_bits, s);
+  radix_passes(sb, 0, key_bits, s, nullptr);
+}
+
+bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows) {
+  // (element indices are 32-bit: the last tile's indices past the rows must not wrap)
+  return key_bits > 0 && !sb->refs[0] && sb->row_refs && rows > 0 && rows <= (int64_t)0xFFFFFFFFll - kRsTile;
+}
+
+void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s) {
+  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb->n), (int)(uint32_t)rows, 1, s);
+  if (e != hipSuccess) {
+    note_launch_error(e);
+    return;
+  }
+  const RsGen gen{d_jobs, njobs, sb->ref_bits};
+  radix_passes(sb, 0, key_bits, s, &gen);
 }
 
 // DG_PROBE_SORT: the headline's sort words — [id0 (17 bits) | id1 (17 bits) | element index], the ids
