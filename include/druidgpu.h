@@ -33,6 +33,10 @@
  *                               (UseIndexesStrategy.java:66-109): IndexOnlyExecutor.execute (:236-281) over
  *                               makeTimeFilteredBitmap (:143-219), or CursorBasedExecutor with
  *                               StringSearchColumnSelectorStrategy.updateSearchResultSet (SearchQueryRunner.java:118-141)
+ *   dg_rows_run / dg_rowset_* <- ScanQueryRunnerFactory.createRunner(segment).run: ScanQueryEngine.process
+ *                               (query/scan/ScanQueryEngine.java:59-264) over the call's segments with the shared
+ *                               limit of mergeRunners (ScanQueryRunnerFactory.java:64-96); the rowset is the
+ *                               columnar form of the ScanResultValue batches (ScanResultValue.java)
  *   dg_result_*              <- the merged grouper's sorted iterator (ConcurrentGrouper.iterator(true))
  *   dg_result_export / dg_keys_partition / dg_merge
  *                            <- QueryRunnerFactory.mergeRunners across devices (query/QueryRunnerFactory.java:62):
@@ -423,6 +427,51 @@ typedef struct {
 typedef struct { const dg_search_dim* dims; int32_t n_dims; int32_t strategy; } dg_search;
 int dg_search_run(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_search* s,
                   int64_t* out_counts, int32_t* out_plan, dg_metrics* metrics);
+
+/* ---- scan (raw rows) ----
+ * The rows a scan query returns (query/scan/ScanQuery.java:53-77, ScanQueryEngine.process :59-264): one
+ * ascending cursor per segment at ALL granularity over filter AND interval (:126-135), the rows in cursor
+ * (= row) order, at most `limit` of them over the call's segments taken in the order given: segment s keeps
+ * its first min(selected_s, limit - kept before s) selected rows (the response context's count, :68-73,:125;
+ * ScanQueryRunnerFactory.mergeRunners :64-96 concatenates in runner order). A segment reached once the limit
+ * is full launches nothing and is not counted in metrics.segment_rows. dg_scan is the cursor struct, so the
+ * query is dg_rows: `scan` supplies the filter, the interval, cancel and timeout_ms; its aggregators,
+ * granularity and `descending` are ignored (the reference's constructor passes descending = false, :67).
+ * columns: the caller's column list (:85-113 is the caller's rule); "__time" names the time column. A name a
+ * segment lacks is DG_COL_MISSING there (null in every row, nothing to fetch); a complex column
+ * (DG_COL_UNSUPPORTED) is DG_ERR_UNSUPPORTED before any launch. The values are what the column selectors'
+ * getObject returns (getColumnValue, :238-250), columnar per (segment, column) and resident in HBM until
+ * fetched page by page or released, like a dg_result:
+ *   LONG and __time  int64            FLOAT  float32            DOUBLE  float64
+ *   STRING, single-value: int32 segment-local dictionary ids (lookupName is the caller's, through
+ *     dg_segment_dim_dictionary: SimpleDictionaryEncodedColumn.java:302-305, null for the empty string)
+ *   STRING, multi-value: the page's ids concatenated + count + 1 offsets relative to the page (the caller
+ *     applies DimensionSelector.defaultGetObject, DimensionSelector.java:167-182: null / the value / the list).
+ *     out_values == NULL writes the offsets only (out_offsets[count] = the ids the page holds).
+ * With no filter and an interval covering the segment's rows there is no selection bitset: the kept rows are
+ * 0 .. keep - 1 and no compaction runs. Only the column blocks holding kept rows are decoded (the block
+ * range [first kept row, last kept row]); a multi-value column is decoded whole.
+ * dg_rowset_rows: rows kept of segment seg (seg < 0: of all). dg_rowset_column_info: *type = DG_COL_*,
+ * *multi, *n_values = values held (rows kept; multi-value: ids). Out-of-range seg / col / start / count and
+ * a NULL out_offsets for a multi-value column -> DG_ERR_ARG.
+ * Metrics: segment_rows, pre_filtered_rows, selected_rows (filter AND interval in the segments scanned,
+ * before the limit), bitmap_bytes, bytes_read (stored bytes of the blocks decoded + bitmaps), bitmap_ms (the
+ * selection), decode_ms, aggregate_ms (compaction + gather kernels), total_ms.
+ * dg_segment_num_dimensions / dg_segment_dimension_name: StorageAdapter.getAvailableDimensions (index.drd's
+ * dimension list; a segment from rows: its string columns in the order given), which the default column
+ * list of a scan puts before the metrics (:96-106). */
+typedef struct { const char* const* columns; int32_t n_columns; int64_t limit; /* <= 0: none */ } dg_rows;
+typedef struct dg_rowset dg_rowset;
+int dg_rows_run(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_rows* spec, dg_rowset** out,
+                dg_metrics* metrics);
+int64_t dg_rowset_rows(const dg_rowset* rs, int32_t seg);
+int dg_rowset_column_info(const dg_rowset* rs, int32_t seg, int32_t col, int32_t* type, int32_t* multi,
+                          int64_t* n_values);
+int dg_rowset_fetch(dg_rowset* rs, int32_t seg, int32_t col, int64_t start, int64_t count, void* out_values,
+                    int64_t* out_offsets);
+void dg_rowset_release(dg_rowset* rs);
+int dg_segment_num_dimensions(const dg_segment* seg);
+const char* dg_segment_dimension_name(const dg_segment* seg, int index);
 
 /* ---- groupBy (v2) ---- */
 /* GroupByStrategyV2.mergeRunners over the call's segments: every segment's rows grouped

@@ -29,6 +29,9 @@ GROUPER_SORT, GROUPER_HASH = 0, 1
 SEARCH_USE_INDEXES, SEARCH_CURSOR_ONLY = 0, 1
 SEARCH_PLAN_NONE, SEARCH_PLAN_INDEX, SEARCH_PLAN_CURSOR = 0, 1, 2
 ERR_TABLE_FULL = 5
+ERR_ARG = 6
+# rows per tile of the scan query's selection -> row number compaction (kRowsTileRows, csrc/dg_internal.h)
+ROWS_TILE_ROWS = 8192
 
 
 class DruidGpuError(RuntimeError):
@@ -130,6 +133,10 @@ class dg_search(ctypes.Structure):
     _fields_ = [("dims", ctypes.POINTER(dg_search_dim)), ("n_dims", ctypes.c_int32), ("strategy", ctypes.c_int32)]
 
 
+class dg_rows(ctypes.Structure):
+    _fields_ = [("columns", ctypes.POINTER(ctypes.c_char_p)), ("n_columns", ctypes.c_int32), ("limit", ctypes.c_int64)]
+
+
 class dg_record_layout(ctypes.Structure):
     _fields_ = [("n_aggs", ctypes.c_int32), ("kinds", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("record_size", ctypes.c_int32), ("big_endian", ctypes.c_int32)]
@@ -169,6 +176,8 @@ EXPORTS = [
     "dg_segment_from_rows", "dg_context_set_limit", "dg_groupby_merge_devices", "dg_timeseries_merge",
     "dg_debug_lz4_classify", "dg_host_alloc", "dg_host_free", "dg_set_phase_timing", "dg_debug_probe",
     "dg_groupby_run_opts", "dg_result_grouper_info", "dg_search_run",
+    "dg_rows_run", "dg_rowset_rows", "dg_rowset_column_info", "dg_rowset_fetch", "dg_rowset_release",
+    "dg_segment_num_dimensions", "dg_segment_dimension_name",
 ]
 
 _lib = None
@@ -223,6 +232,13 @@ def lib():
                                                P(dg_metrics)]),
         "dg_result_grouper_info": (ctypes.c_int, [vp, P(dg_grouper_info)]),
         "dg_search_run": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_search), vp, vp, P(dg_metrics)]),
+        "dg_rows_run": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_rows), P(vp), P(dg_metrics)]),
+        "dg_rowset_rows": (i64, [vp, i32]),
+        "dg_rowset_column_info": (ctypes.c_int, [vp, i32, i32, P(i32), P(i32), P(i64)]),
+        "dg_rowset_fetch": (ctypes.c_int, [vp, i32, i32, i64, i64, vp, vp]),
+        "dg_rowset_release": (None, [vp]),
+        "dg_segment_num_dimensions": (ctypes.c_int, [vp]),
+        "dg_segment_dimension_name": (cp, [vp, ctypes.c_int]),
         "dg_result_groups": (i64, [vp]),
         "dg_result_fetch_groups": (ctypes.c_int, [vp, i64, i64, vp, vp, vp]),
         "dg_result_fetch_rows": (ctypes.c_int, [vp, i64, i64, vp]),
@@ -428,3 +444,56 @@ def make_scan(query, query_module, cancel: Optional[ctypes.c_int32] = None, segm
     # QueryContexts.getTimeout: the context's "timeout" (ms; 0 = none)
     s.timeout_ms = int((getattr(query, "context", None) or {}).get("timeout", 0) or 0)
     return s, keep
+
+
+_ROWSET_DTYPES = {COL_LONG: np.int64, COL_FLOAT: np.float32, COL_DOUBLE: np.float64, COL_STRING: np.int32}
+
+
+class RowSet:
+    """A dg_rowset: the kept rows of a dg_rows_run call, columnar per (segment, column) and resident in HBM
+    until fetched page by page or closed."""
+
+    def __init__(self, handle: ctypes.c_void_p, n_segs: int, n_cols: int):
+        self.handle, self.n_segs, self.n_cols = handle, n_segs, n_cols
+
+    def rows(self, seg: int = -1) -> int:
+        return int(lib().dg_rowset_rows(self.handle, seg))
+
+    def column_info(self, seg: int, col: int):
+        """(DG_COL_* type, multi-value?, values held)."""
+        t, mv, nv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        check(lib().dg_rowset_column_info(self.handle, seg, col, ctypes.byref(t), ctypes.byref(mv), ctypes.byref(nv)))
+        return t.value, bool(mv.value), nv.value
+
+    def fetch(self, seg: int, col: int, start: int = 0, count: Optional[int] = None):
+        """Rows [start, start + count) of one column: (values, offsets). values: int64 / float32 / float64
+        / int32 dictionary ids, None for a column the segment lacks; offsets: None, or for a multi-value
+        column count + 1 list starts into values, relative to the page."""
+        typ, multi, _ = self.column_info(seg, col)
+        if count is None:
+            count = self.rows(seg) - start
+        L = lib()
+        if typ == COL_MISSING:
+            check(L.dg_rowset_fetch(self.handle, seg, col, start, count, None, None))  # (the range is still checked)
+            return None, None
+        if not multi:
+            vals = np.empty(max(count, 0), dtype=_ROWSET_DTYPES[typ])
+            check(L.dg_rowset_fetch(self.handle, seg, col, start, count, vals.ctypes.data, None))
+            return vals, None
+        offs = np.zeros(max(count, 0) + 1, dtype=np.int64)
+        check(L.dg_rowset_fetch(self.handle, seg, col, start, count, None, offs.ctypes.data))  # sizes the page
+        vals = np.empty(int(offs[-1]), dtype=np.int32)
+        if len(vals):
+            check(L.dg_rowset_fetch(self.handle, seg, col, start, count, vals.ctypes.data, offs.ctypes.data))
+        return vals, offs
+
+    def close(self):
+        if self.handle:
+            lib().dg_rowset_release(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

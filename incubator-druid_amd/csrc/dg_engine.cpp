@@ -1273,8 +1273,10 @@ static void add_tasks(DecodeBatch* db, const BlockColumn& b, int32_t k0, int32_t
   }
 }
 
+// kb0 / kb1: the blocks [kb0, kb1) the caller will read (kb1 < 0: all of them); the others are neither
+// decoded nor given a pointer (the scan query's block pruning)
 static int block_view(const BlockColumn& b, int kind, const char* name, CallScratch* cs, DecodeBatch* db, ColView* v,
-                      hipStream_t st);
+                      hipStream_t st, int32_t kb0 = 0, int32_t kb1 = -1);
 
 static int column_view(const Column* c, CallScratch* cs, DecodeBatch* db, ColView* v, hipStream_t st) {
   if (c->multi_value)
@@ -1301,24 +1303,37 @@ static int multi_view(const Column* c, CallScratch* cs, DecodeBatch* db, ColView
 }
 
 static int block_view(const BlockColumn& b, int kind, const char* name, CallScratch* cs, DecodeBatch* db, ColView* v,
-                      hipStream_t st) {
+                      hipStream_t st, int32_t kb0, int32_t kb1) {
   v->log2_per = b.log2_per;
   v->width = b.width;
   v->pad = b.big_endian ? kViewBigEndian : 0;
   v->kind = kind;
-  db->bytes += b.stored_bytes + b.index_bytes;
+  if (kb1 < 0 || kb1 > b.nblocks) kb1 = b.nblocks;
+  kb0 = std::max(0, std::min(kb0, kb1));
+  const bool whole = kb0 == 0 && kb1 == b.nblocks;
+  const int32_t nb = kb1 - kb0;
+  if (whole) {
+    db->bytes += b.stored_bytes + b.index_bytes;
+  } else if (b.nblocks > 0) {  // the stored bytes of the blocks read (their share of the index)
+    int64_t stored = 0;
+    if ((int32_t)b.comp_len.size() == b.nblocks)
+      for (int32_t k = kb0; k < kb1; ++k) stored += b.comp_len[k];
+    else
+      stored = b.stored_bytes * nb / b.nblocks;
+    db->bytes += stored + b.index_bytes * nb / b.nblocks;
+  }
   if (b.codec != CODEC_LZ4 && b.codec != CODEC_LZF && b.codec != CODEC_UNCOMPRESSED && b.codec != CODEC_NONE)
     return set_error(DG_ERR_UNSUPPORTED, "codec 0x%02x of %s", b.codec, name);
   uint8_t* slots = nullptr;
   const int routes = b.codec == CODEC_LZ4 ? decode_routes() : 0;
   if (b.codec == CODEC_LZ4 || b.codec == CODEC_LZF) {
-    slots = dev_take<uint8_t>(cs, (size_t)b.nblocks * kBlockBytes + 64);
+    slots = dev_take<uint8_t>(cs, (size_t)nb * kBlockBytes + 64);
     if (!slots) return set_error(DG_ERR_OOM, "decode scratch");
     db->last_slots = slots;
   }
   int64_t* expanded = nullptr;
   if (b.vbits) {
-    expanded = dev_take<int64_t>(cs, (size_t)b.nblocks * b.size_per + 8);
+    expanded = dev_take<int64_t>(cs, (size_t)nb * b.size_per + 8);
     if (!expanded) return set_error(DG_ERR_OOM, "expand scratch");
     db->last_expanded = expanded;
   }
@@ -1329,18 +1344,25 @@ static int block_view(const BlockColumn& b, int kind, const char* name, CallScra
   const uint8_t** d_ptrs;
   const uint8_t** h_ptrs = up_take<const uint8_t*>(cs, std::max(b.nblocks, 1), &d_ptrs, st);
   if (!h_ptrs || !d_ptrs) return set_error(DG_ERR_OOM, "decode scratch");
-  const bool tasks = taskable(b, routes);  // every LZ4 block decodes to its slot k: one task per kind
-  if (tasks) add_tasks(db, b, 0, b.nblocks, slots, kBlockBytes, 0, nullptr);
+  const bool tasks = taskable(b, routes);  // every LZ4 block decodes to its slot: one task per kind
+  // (block k's slot is slots + (k - kb0) * kBlockBytes: the task's base is the slot block 0 would have)
+  if (tasks && nb > 0)
+    add_tasks(db, b, kb0, kb1, reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(slots) - (uintptr_t)kb0 * kBlockBytes),
+              kBlockBytes, 0, nullptr);
   for (int32_t k = 0; k < b.nblocks; ++k) {
+    if (k < kb0 || k >= kb1) {
+      h_ptrs[k] = nullptr;  // never read: no kept row lies in it
+      continue;
+    }
     const int64_t rows = std::min<int64_t>(b.size_per, (int64_t)b.total - (int64_t)k * b.size_per);
     // the packed (or plain) bytes of block k: an LZ4 slot, an uncompressed slot or a NONE range
     const uint8_t* src;
     const uint8_t* lit = literal_block(b, k);
     if (lit) src = lit;
-    else if (slots) src = slots + (size_t)k * kBlockBytes;
+    else if (slots) src = slots + (size_t)(k - kb0) * kBlockBytes;
     else if (b.codec == CODEC_UNCOMPRESSED) src = b.raw.as<uint8_t>() + (size_t)k * kBlockBytes;
     else src = b.raw.as<uint8_t>() + (size_t)k * (size_t)b.size_per * b.vbits / 8;
-    h_ptrs[k] = expanded ? reinterpret_cast<const uint8_t*>(expanded + (size_t)k * b.size_per) : src;
+    h_ptrs[k] = expanded ? reinterpret_cast<const uint8_t*>(expanded + (size_t)(k - kb0) * b.size_per) : src;
     if (rows <= 0) continue;
     if (slots && !lit && !tasks) {
       const int64_t expect = b.vbits ? (b.vbits * rows + 7) / 8 : rows * b.width;
@@ -1358,7 +1380,7 @@ static int block_view(const BlockColumn& b, int kind, const char* name, CallScra
     if (expanded) {
       VsJob e;
       e.src = src;
-      e.dst = expanded + (size_t)k * b.size_per;
+      e.dst = expanded + (size_t)(k - kb0) * b.size_per;
       e.table = b.table.p ? b.table.as<int64_t>() : nullptr;
       e.base = b.delta_base;
       e.rows = (int32_t)rows;
@@ -2468,6 +2490,14 @@ const char* dg_segment_column_name(const dg_segment* s, int i) {
   const Segment* seg = reinterpret_cast<const Segment*>(s);
   if (i < 0 || i >= (int)seg->columns.size()) return nullptr;
   return seg->columns[i]->name.c_str();
+}
+
+int dg_segment_num_dimensions(const dg_segment* s) { return (int)reinterpret_cast<const Segment*>(s)->dims.size(); }
+
+const char* dg_segment_dimension_name(const dg_segment* s, int i) {
+  const Segment* seg = reinterpret_cast<const Segment*>(s);
+  if (i < 0 || i >= (int)seg->dims.size()) return nullptr;
+  return seg->dims[i].c_str();
 }
 
 int dg_segment_column_type(const dg_segment* s, const char* col) {
@@ -4884,6 +4914,482 @@ int32_t dg_result_dim_cardinality(const dg_result* r, int32_t dim) {
 }
 
 void dg_result_release(dg_result* r) { delete r; }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// scan query: the rows themselves (query/scan/ScanQueryEngine.java:59-264). The rowset is the columnar,
+// HBM-resident form of the engine's ScanResultValue batches: per (segment, column) the kept rows' values.
+// ------------------------------------------------------------------------------------------------
+struct dg_rowset {
+  dg::Context* ctx = nullptr;
+  int nsegs = 0, ncols = 0;
+  std::vector<int64_t> rows;  // rows kept per segment
+  struct Col {
+    int32_t type = DG_COL_MISSING;
+    int32_t multi = 0;
+    int32_t width = 0;     // bytes per value (multi-value: per id)
+    int64_t n_values = 0;  // values held (rows kept; multi-value: ids)
+    uint8_t* data = nullptr;
+    int64_t* offs = nullptr;  // multi-value: [rows + 1] list starts into data
+  };
+  std::vector<Col> cols;      // [seg * ncols + col]
+  std::vector<void*> blocks;  // device blocks (result_alloc)
+  void drop() {               // (under the context's lock)
+    for (void* p : blocks) dg::result_free(ctx, p);
+    blocks.clear();
+  }
+  ~dg_rowset() {
+    if (!ctx) return;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    hipSetDevice(ctx->device);
+    drop();
+  }
+};
+
+// a rowset under construction inside a call (see ResultDrop)
+struct RowsetDrop {
+  void operator()(dg_rowset* r) const {
+    if (!r) return;
+    if (r->ctx) r->drop();
+    r->ctx = nullptr;
+    delete r;
+  }
+};
+
+namespace dg {
+constexpr size_t kRowsScratchBudget = (size_t)256 << 20;  // decode scratch of one column group of a scan
+
+struct PoolMark {
+  size_t cur, off;
+};
+}  // namespace dg
+
+extern "C" {
+
+int dg_rows_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_rows* spec, dg_rowset** out,
+                dg_metrics* metrics) {
+  auto t0 = std::chrono::steady_clock::now();
+  Context* ctx;
+  int rc = check_segments(segs, n, &ctx);
+  if (rc) return rc;
+  if (!q || !spec || !out) return set_error(DG_ERR_ARG, "null argument");
+  *out = nullptr;
+  const int nc = spec->n_columns;
+  if (nc < 0 || (nc > 0 && !spec->columns)) return set_error(DG_ERR_ARG, "scan columns");
+  for (int c = 0; c < nc; ++c)
+    if (!spec->columns[c]) return set_error(DG_ERR_ARG, "scan column %d is null", c);
+  // the scan without its granularity and aggregators: one ascending cursor over the interval
+  dg_scan qs = *q;
+  qs.period_ms = 0;
+  qs.origin_ms = 0;
+  qs.bucket_starts = nullptr;
+  qs.n_bucket_starts = 0;
+  qs.seg_bounds = nullptr;
+  qs.descending = 0;
+  qs.aggs = nullptr;
+  qs.n_aggs = 0;
+  q = &qs;
+  const Grain gr;
+  const bool limited = spec->limit > 0;
+  const int64_t limit = limited ? spec->limit : INT64_MAX;
+  // every column is resolved before anything is launched
+  std::vector<const Column*> cols((size_t)n * nc, nullptr);
+  for (int i = 0; i < n; ++i) {
+    const Segment* seg = reinterpret_cast<const Segment*>(segs[i]);
+    for (int c = 0; c < nc; ++c) {
+      const Column* col = seg->find(spec->columns[c]);
+      if (col && col->type == DG_COL_UNSUPPORTED)
+        return set_error(DG_ERR_UNSUPPORTED, "scan column %s is a complex column (or an unsupported codec)",
+                         spec->columns[c]);
+      cols[(size_t)i * nc + c] = col && col->type != DG_COL_MISSING ? col : nullptr;
+    }
+  }
+  CallGuard g(ctx);
+  CallScratch* cs = g.cs;
+  Interrupt intr(q, t0);
+  cs->intr = &intr;
+  hipStream_t st = ctx->stream;
+  dg_metrics m;
+  memset(&m, 0, sizeof m);
+  std::unique_ptr<dg_rowset, RowsetDrop> rs(new dg_rowset());
+  rs->ctx = ctx;
+  rs->nsegs = n;
+  rs->ncols = nc;
+  rs->rows.assign(n, 0);
+  rs->cols.resize((size_t)n * nc);
+  for (size_t x = 0; x < cols.size(); ++x) {
+    if (!cols[x]) continue;
+    dg_rowset::Col& rc_ = rs->cols[x];
+    rc_.type = cols[x]->type;
+    rc_.multi = cols[x]->multi_value ? 1 : 0;
+    rc_.width = cols[x]->type == DG_COL_LONG || cols[x]->type == DG_COL_DOUBLE ? 8 : 4;
+  }
+  struct SegSel {
+    bool live = false, timed = false;
+    uint32_t* filter_bits = nullptr;
+    uint32_t* sel = nullptr;  // S (null: every row)
+    ColView time;
+    int64_t t_lo = 0, t_hi = 0;
+    const unsigned long long* pre = nullptr;
+    unsigned long long *d_cnt = nullptr, *h_cnt = nullptr;    // rows the interval test selects (metrics)
+    unsigned long long *d_info = nullptr, *h_info = nullptr;  // launch_rows_select's info words
+    uint32_t* d_rows = nullptr;                               // kept row numbers (null: rows 0 .. keep - 1)
+    int64_t keep = 0, first = 0, last = 0;
+  };
+  std::vector<SegSel> sp(n);
+  int64_t kept = 0, decoded_bytes = 0;
+  double bitmap_ms = 0, decode_ms = 0, aggregate_ms = 0;
+  DecodeBatch all;  // the call's decode metrics (every batch's general-decoder counts)
+  auto fold_batch = [&](const DecodeBatch& db) {
+    decoded_bytes += db.bytes;
+    all.gen_bytes += db.gen_bytes;
+    all.gen_blocks += db.gen_blocks;
+    all.gen_launches += db.gen_launches;
+    all.flow_blocks += db.flow_blocks;
+    all.flow_bytes += db.flow_bytes;
+  };
+  // ---- selection: waves of segments (all of them without a limit; one at a time with one, so that a
+  // segment reached after the limit is full launches nothing), one read-back of the counts per wave ----
+  for (int w0 = 0; w0 < n && kept < limit;) {
+    const int w1 = limited ? w0 + 1 : n;
+    DecodeBatch db;
+    decode_events(ctx, &db, false);
+    phase_event(ctx->ev[0], st);
+    for (int i = w0; i < w1; ++i) {
+      Segment* seg = reinterpret_cast<Segment*>(segs[i]);
+      m.segment_rows += seg->nrows;
+      const Cursors cu = plan_cursors(seg, i, q, gr);
+      if (!cu.any) continue;  // no row of the segment lies in the interval
+      SegSel& p = sp[i];
+      p.live = true;
+      rc = build_bitset(seg, cs, q->filter, q->n_filter, &p.filter_bits, &p.pre, st);
+      if (rc) return rc;
+      p.sel = p.filter_bits;
+      if (cu.need_time) {
+        const Column* tcol = seg->find("__time");
+        if (!tcol) return set_error(DG_ERR_FORMAT, "segment without __time");
+        const std::vector<int64_t> tb = time_block_buckets(seg, tcol, cu, 0, gr);
+        rc = time_view(tcol, tb, cs, &db, &p.time, st);
+        if (rc) return rc;
+        p.sel = dev_take<uint32_t>(cs, (size_t)((seg->nrows + 31) / 32) + 2);
+        unsigned long long* z = up_take<unsigned long long>(cs, 1, &p.d_cnt, st);
+        p.h_cnt = host_take<unsigned long long>(cs, 1);
+        if (!p.sel || !z || !p.h_cnt) return set_error(DG_ERR_OOM, "selection bitset");
+        *z = 0;
+        p.timed = true;
+        p.t_lo = cu.t_lo;
+        p.t_hi = cu.t_hi;
+        cs->bitmap_bytes += (seg->nrows + 31) / 32 * 4 * (p.filter_bits ? 2 : 1);
+      }
+      if (p.sel) {
+        unsigned long long* z = up_take<unsigned long long>(cs, 4, &p.d_info, st);
+        p.h_info = host_take<unsigned long long>(cs, 4);
+        if (!z || !p.h_info) return set_error(DG_ERR_OOM, "selection counts");
+        memset(z, 0, 32);
+      }
+    }
+    DG_CHECK_INTERRUPT(intr);
+    phase_event(ctx->ev[1], st);
+    rc = run_decodes(cs, &db, st);
+    if (rc) return rc;
+    phase_event(ctx->ev[2], st);
+    DG_CHECK_INTERRUPT(intr);
+    DG_FLUSH(cs, st);
+    for (int i = w0; i < w1; ++i)
+      if (sp[i].timed)
+        launch_search_time_and(sp[i].time, sp[i].filter_bits, reinterpret_cast<Segment*>(segs[i])->nrows, sp[i].t_lo,
+                               sp[i].t_hi, sp[i].sel, sp[i].d_cnt, st);
+    phase_event(ctx->ev[3], st);
+    for (int i = w0; i < w1; ++i) {
+      SegSel& p = sp[i];
+      if (!p.live || !p.sel) continue;
+      const int64_t nrows = reinterpret_cast<Segment*>(segs[i])->nrows;
+      const int64_t cap = std::min<int64_t>(nrows, limit - kept);  // (a limited wave holds one segment)
+      const int64_t ntiles = ((nrows + 31) / 32 + kRowsTileWords - 1) / kRowsTileWords;
+      uint32_t* tile_cnt = dev_take<uint32_t>(cs, (size_t)std::max<int64_t>(ntiles, 1));
+      p.d_rows = dev_take<uint32_t>(cs, (size_t)std::max<int64_t>(cap, 1));
+      if (!tile_cnt || !p.d_rows) return set_error(DG_ERR_OOM, "row numbers");
+      launch_rows_select(p.sel, nrows, (uint64_t)cap, tile_cnt, p.d_info, p.d_rows, st);
+      cs->late.push_back({p.h_info, p.d_info, 32});
+      if (p.timed) cs->late.push_back({p.h_cnt, p.d_cnt, 8});
+      cs->bitmap_bytes += 2 * ((nrows + 31) / 32 * 4);  // the selection read by the count and by the emit
+    }
+    phase_event(ctx->ev[4], st);
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    for (int i = w0; i < w1; ++i) {
+      SegSel& p = sp[i];
+      if (!p.live) continue;
+      const int64_t nrows = reinterpret_cast<Segment*>(segs[i])->nrows;
+      const int64_t pre = p.pre ? (int64_t)*p.pre : nrows;
+      m.pre_filtered_rows += pre;
+      if (p.sel) {
+        m.selected_rows += (int64_t)p.h_info[0];
+        p.keep = (int64_t)p.h_info[1];
+        p.first = (int64_t)p.h_info[2];
+        p.last = (int64_t)p.h_info[3];
+      } else {  // no filter, the interval covers the segment: rows 0 .. keep - 1, no compaction
+        m.selected_rows += nrows;
+        p.keep = std::min<int64_t>(nrows, limit - kept);
+        p.first = 0;
+        p.last = p.keep - 1;
+      }
+      if (p.keep < 0 || p.keep > nrows || (p.keep > 0 && (p.first > p.last || p.last >= nrows)))
+        return set_error(DG_ERR_DEVICE, "inconsistent selection counts");
+      kept += p.keep;
+      rs->rows[i] = p.keep;
+    }
+    float f1 = 0, f2 = 0, f3 = 0, f4 = 0;
+    phase_elapsed(&f1, ctx->ev[0], ctx->ev[1]);
+    phase_elapsed(&f2, ctx->ev[1], ctx->ev[2]);
+    phase_elapsed(&f3, ctx->ev[2], ctx->ev[3]);
+    phase_elapsed(&f4, ctx->ev[3], ctx->ev[4]);
+    bitmap_ms += f1 + f3;  // the filter's bitset + the interval test
+    decode_ms += f2;
+    aggregate_ms += f4;  // the compaction
+    fold_batch(db);
+    w0 = w1;
+  }
+  // ---- the result arena of the fixed-width columns, sized from the counts ----
+  size_t arena = 0;
+  for (int i = 0; i < n; ++i)
+    for (int c = 0; c < nc; ++c) {
+      dg_rowset::Col& rc_ = rs->cols[(size_t)i * nc + c];
+      if (rc_.type == DG_COL_MISSING || rc_.multi) continue;
+      rc_.n_values = sp[i].keep;
+      arena += ((size_t)sp[i].keep * rc_.width + 255) & ~(size_t)255;
+    }
+  if (arena) {
+    uint8_t* base = static_cast<uint8_t*>(result_alloc(ctx, arena));
+    if (!base) {
+      (void)hipGetLastError();
+      return set_error(DG_ERR_OOM, "scan result of %zu bytes", arena);
+    }
+    rs->blocks.push_back(base);
+    size_t at = 0;
+    for (int i = 0; i < n; ++i)
+      for (int c = 0; c < nc; ++c) {
+        dg_rowset::Col& rc_ = rs->cols[(size_t)i * nc + c];
+        if (rc_.type == DG_COL_MISSING || rc_.multi || sp[i].keep == 0) continue;
+        rc_.data = base + at;
+        at += ((size_t)sp[i].keep * rc_.width + 255) & ~(size_t)255;
+      }
+  }
+  // ---- gather: the fixed-width columns in groups whose decode scratch fits kRowsScratchBudget (at least
+  // one column each). A group's slots are given back once its gathers have run, so the next group
+  // decodes into the same memory: a wide scan never holds every column's decoded image at once. Only
+  // the blocks [first kept row, last kept row] of a column are decoded. ----
+  struct Item {
+    int seg, col;
+    int32_t k0, k1;
+    size_t scratch;
+  };
+  std::vector<Item> items;
+  for (int i = 0; i < n; ++i) {
+    if (sp[i].keep <= 0) continue;
+    for (int c = 0; c < nc; ++c) {
+      const Column* col = cols[(size_t)i * nc + c];
+      if (!col || col->multi_value) continue;
+      const BlockColumn& b = col->data;
+      Item it;
+      it.seg = i;
+      it.col = c;
+      it.k0 = (int32_t)(sp[i].first >> b.log2_per);
+      it.k1 = std::min<int32_t>(b.nblocks, (int32_t)(sp[i].last >> b.log2_per) + 1);
+      const size_t nb = (size_t)std::max(0, it.k1 - it.k0);
+      it.scratch = ((b.codec == CODEC_LZ4 || b.codec == CODEC_LZF) ? nb * kBlockBytes : 0) +
+                   (b.vbits ? nb * (size_t)b.size_per * 8 : 0);
+      items.push_back(it);
+    }
+  }
+  const PoolMark mark{cs->dev.cur, cs->dev.off};
+  for (size_t g0 = 0; g0 < items.size();) {
+    size_t g1 = g0, sum = 0;
+    while (g1 < items.size() && (g1 == g0 || sum + items[g1].scratch <= kRowsScratchBudget)) sum += items[g1++].scratch;
+    DG_CHECK_INTERRUPT(intr);
+    DecodeBatch db;
+    decode_events(ctx, &db, false);
+    phase_event(ctx->ev[0], st);
+    struct Launch {
+      RowsCol* d_tbl;
+      int ncols, seg;
+    };
+    std::vector<Launch> launches;
+    for (size_t x = g0; x < g1;) {
+      size_t y = x;
+      while (y < g1 && items[y].seg == items[x].seg) ++y;
+      Launch L;
+      L.seg = items[x].seg;
+      L.ncols = (int)(y - x);
+      RowsCol* h_tbl = up_take<RowsCol>(cs, y - x, &L.d_tbl, st);
+      if (!h_tbl) return set_error(DG_ERR_OOM, "gather table");
+      for (size_t z = x; z < y; ++z) {
+        const Item& it = items[z];
+        const Column* col = cols[(size_t)it.seg * nc + it.col];
+        const int kind = col->type == DG_COL_LONG ? VIEW_LONG : col->type == DG_COL_DOUBLE ? VIEW_DOUBLE
+                         : col->type == DG_COL_FLOAT ? VIEW_FLOAT : VIEW_IDS;
+        memset(&h_tbl[z - x], 0, sizeof(RowsCol));
+        rc = block_view(col->data, kind, col->name.c_str(), cs, &db, &h_tbl[z - x].v, st, it.k0, it.k1);
+        if (rc) return rc;
+        h_tbl[z - x].out = rs->cols[(size_t)it.seg * nc + it.col].data;
+      }
+      launches.push_back(L);
+      x = y;
+    }
+    rc = run_decodes(cs, &db, st);
+    if (rc) return rc;
+    phase_event(ctx->ev[1], st);
+    DG_CHECK_INTERRUPT(intr);
+    DG_FLUSH(cs, st);
+    for (const Launch& L : launches) launch_rows_gather(L.d_tbl, L.ncols, sp[L.seg].d_rows, sp[L.seg].keep, st);
+    phase_event(ctx->ev[2], st);
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    float f1 = 0, f2 = 0;
+    phase_elapsed(&f1, ctx->ev[0], ctx->ev[1]);
+    phase_elapsed(&f2, ctx->ev[1], ctx->ev[2]);
+    decode_ms += f1;
+    aggregate_ms += f2;
+    fold_batch(db);
+    cs->dev.cur = mark.cur;  // (the stream is idle: the group's slots are free again)
+    cs->dev.off = mark.off;
+    g0 = g1;
+  }
+  // ---- multi-value columns, one (segment, column) at a time: the row lists are validated (k_mv_check),
+  // the kept rows' lengths summed, the result sized from that sum, then the ids copied. The column is
+  // decoded whole: which value blocks the kept rows reach is only known from the decoded offsets. ----
+  for (int i = 0; i < n; ++i) {
+    if (sp[i].keep <= 0) continue;
+    for (int c = 0; c < nc; ++c) {
+      const Column* col = cols[(size_t)i * nc + c];
+      if (!col || !col->multi_value) continue;
+      DG_CHECK_INTERRUPT(intr);
+      dg_rowset::Col& rc_ = rs->cols[(size_t)i * nc + c];
+      const int64_t keep = sp[i].keep;
+      DecodeBatch db;
+      decode_events(ctx, &db, false);
+      RowsMv mv;
+      memset(&mv, 0, sizeof mv);
+      phase_event(ctx->ev[0], st);
+      rc = multi_view(col, cs, &db, &mv.vals, &mv.offs, st);
+      if (rc) return rc;
+      mv.rows = sp[i].d_rows;
+      mv.keep = keep;
+      mv.nvals = col->data.total;
+      mv.tile_off = dev_take<uint32_t>(cs, (size_t)((keep + 255) / 256));
+      unsigned long long* d_info;
+      unsigned long long* z = up_take<unsigned long long>(cs, 2, &d_info, st);
+      unsigned long long* h_info = host_take<unsigned long long>(cs, 2);
+      if (!mv.tile_off || !z || !h_info) return set_error(DG_ERR_OOM, "multi-value scratch");
+      z[0] = z[1] = 0;
+      rc = run_decodes(cs, &db, st);  // (waits for the row lists' verdict)
+      if (rc) return rc;
+      phase_event(ctx->ev[1], st);
+      DG_FLUSH(cs, st);
+      launch_rows_mv_len(mv, d_info, st);
+      cs->late.push_back({h_info, d_info, 16});
+      rc = finish_call(cs, st);
+      if (rc) return rc;
+      const int64_t nvals = (int64_t)h_info[0];
+      if (nvals < 0 || nvals > (int64_t)col->data.total)  // (distinct rows of validated, ascending offsets)
+        return set_error(DG_ERR_DEVICE, "inconsistent value counts");
+      const size_t obytes = (((size_t)keep + 1) * 8 + 255) & ~(size_t)255;
+      uint8_t* blk = static_cast<uint8_t*>(result_alloc(ctx, obytes + (size_t)std::max<int64_t>(nvals, 1) * 4));
+      if (!blk) {
+        (void)hipGetLastError();
+        return set_error(DG_ERR_OOM, "scan result of %lld values", (long long)nvals);
+      }
+      rs->blocks.push_back(blk);
+      rc_.offs = reinterpret_cast<int64_t*>(blk);
+      rc_.data = blk + obytes;
+      rc_.n_values = nvals;
+      mv.out_offs = rc_.offs;
+      mv.out_ids = reinterpret_cast<int32_t*>(rc_.data);
+      mv.out_cap = nvals;
+      launch_rows_mv_copy(mv, st);
+      phase_event(ctx->ev[2], st);
+      rc = finish_call(cs, st);
+      if (rc) return rc;
+      float f1 = 0, f2 = 0;
+      phase_elapsed(&f1, ctx->ev[0], ctx->ev[1]);
+      phase_elapsed(&f2, ctx->ev[1], ctx->ev[2]);
+      decode_ms += f1;
+      aggregate_ms += f2;
+      fold_batch(db);
+      cs->dev.cur = mark.cur;
+      cs->dev.off = mark.off;
+    }
+  }
+  m.bitmap_ms = bitmap_ms;
+  m.decode_ms = decode_ms;
+  m.aggregate_ms = aggregate_ms;
+  m.bitmap_bytes = cs->bitmap_bytes;
+  m.bytes_read = decoded_bytes + cs->bitmap_bytes;
+  m.lz4_general_bytes = all.gen_bytes;
+  m.lz4_general_blocks = all.gen_blocks;
+  m.lz4_general_launches = all.gen_launches;
+  m.lz4_flow_blocks = all.flow_blocks;
+  m.lz4_flow_bytes = all.flow_bytes;
+  m.total_ms = ms_since(t0);
+  if (metrics) *metrics = m;
+  *out = rs.release();
+  return DG_OK;
+}
+
+int64_t dg_rowset_rows(const dg_rowset* rs, int32_t seg) {
+  if (!rs || seg >= rs->nsegs) return -1;
+  if (seg >= 0) return rs->rows[seg];
+  int64_t t = 0;
+  for (int64_t r : rs->rows) t += r;
+  return t;
+}
+
+int dg_rowset_column_info(const dg_rowset* rs, int32_t seg, int32_t col, int32_t* type, int32_t* multi, int64_t* n_values) {
+  if (!rs || seg < 0 || seg >= rs->nsegs || col < 0 || col >= rs->ncols)
+    return set_error(DG_ERR_ARG, "rowset column (%d, %d)", seg, col);
+  const dg_rowset::Col& c = rs->cols[(size_t)seg * rs->ncols + col];
+  if (type) *type = c.type;
+  if (multi) *multi = c.multi;
+  if (n_values) *n_values = c.n_values;
+  return DG_OK;
+}
+
+int dg_rowset_fetch(dg_rowset* rs, int32_t seg, int32_t col, int64_t start, int64_t count, void* out_values,
+                    int64_t* out_offsets) {
+  if (!rs || seg < 0 || seg >= rs->nsegs || col < 0 || col >= rs->ncols)
+    return set_error(DG_ERR_ARG, "rowset column (%d, %d)", seg, col);
+  const dg_rowset::Col& c = rs->cols[(size_t)seg * rs->ncols + col];
+  const int64_t rows = rs->rows[seg];
+  if (start < 0 || count < 0 || start > rows || count > rows - start) return set_error(DG_ERR_ARG, "bad rowset range");
+  if (c.type == DG_COL_MISSING) return DG_OK;  // null in every row: nothing to fetch
+  if (c.multi && !out_offsets) return set_error(DG_ERR_ARG, "a multi-value column needs out_offsets");
+  if (!c.multi && !out_values && count > 0) return set_error(DG_ERR_ARG, "null out_values");
+  if (count == 0) {
+    if (c.multi) out_offsets[0] = 0;
+    return DG_OK;
+  }
+  CallGuard g(rs->ctx);
+  hipStream_t st = rs->ctx->stream;
+  if (!c.multi) {
+    DG_HIP(hipMemcpyAsync(out_values, c.data + (size_t)start * c.width, (size_t)count * c.width, hipMemcpyDeviceToHost, st));
+    return finish_call(g.cs, st);
+  }
+  DG_HIP(hipMemcpyAsync(out_offsets, c.offs + start, ((size_t)count + 1) * 8, hipMemcpyDeviceToHost, st));
+  int rc = finish_call(g.cs, st);
+  if (rc) return rc;
+  const int64_t base = out_offsets[0], nv = out_offsets[count] - base;
+  if (base < 0 || nv < 0 || base + nv > c.n_values) return set_error(DG_ERR_DEVICE, "inconsistent rowset offsets");
+  if (out_values && nv > 0) {
+    DG_HIP(hipMemcpyAsync(out_values, c.data + (size_t)base * 4, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+    rc = finish_call(g.cs, st);
+    if (rc) return rc;
+  }
+  for (int64_t k = 0; k <= count; ++k) out_offsets[k] -= base;
+  return DG_OK;
+}
+
+void dg_rowset_release(dg_rowset* rs) { delete rs; }
 
 // ---- BufferAggregator records ----
 int dg_records_pack(const uint64_t* slots, int64_t n, const dg_record_layout* lay, void* out) {

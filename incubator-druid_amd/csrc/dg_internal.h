@@ -484,6 +484,9 @@ struct Segment {
   int bitmap_roaring = 0;
   std::vector<std::unique_ptr<Column>> columns;
   std::map<std::string, Column*> by_name;
+  // the dimension list (index.drd's `dims`, StorageAdapter.getAvailableDimensions; a segment from rows:
+  // its string columns in the order given): the scan query's default column list puts them first
+  std::vector<std::string> dims;
   int64_t device_bytes = 0;
   Column* find(const std::string& n) const {
     auto it = by_name.find(n);
@@ -600,6 +603,38 @@ void launch_search_roaring_count(const SearchJob* d_jobs, int n_whole, int n_job
                                  int32_t* d_err, hipStream_t s);
 // the histogram of one (segment, dimension) and the gather of its accepted ids' counters into d_out[0, n_ids)
 void launch_search_hist(const SearchHist& h, const int32_t* d_ids, int n_ids, unsigned long long* d_out, hipStream_t s);
+// ---- scan query (dg_rows.hip) ----
+// Tile of the selection -> row number compaction: kRowsTileWords 32-bit bitset words, one per thread
+// (8192 rows per workgroup).
+constexpr int kRowsTileWords = 256;
+constexpr int kRowsTileRows = kRowsTileWords * 32;
+// one fixed-width column of a gather launch: the kept rows' values go to out[0 .. keep) as int64 / double
+// (8-byte views), float32 (4-byte views) or int32 dictionary ids (id views of any stored width)
+struct RowsCol {
+  ColView v;
+  void* out;
+};
+// one multi-value column of one segment: the kept rows' value lists
+struct RowsMv {
+  ColView vals;          // the value ids
+  ColView offs;          // rows + 1 offsets into vals
+  const uint32_t* rows;  // kept row numbers (null: rows 0 .. keep - 1)
+  int64_t keep;
+  int64_t nvals;         // values stored (offsets are clamped to it)
+  uint32_t* tile_off;    // [ceil(keep / 256)] values per tile of 256 kept rows, then their exclusive offsets
+  int64_t* out_offs;     // [keep + 1] list starts in out_ids (k_rows_mv_copy)
+  int32_t* out_ids;      // [out_cap]
+  int64_t out_cap;
+};
+// S -> the first min(|S|, cap) selected rows, ascending, in rows; tile_cnt: ceil(ceil(nrows / 32) /
+// kRowsTileWords) words; info (zeroed): [0] = |S|, [1] = rows kept, [2] / [3] = first / last kept row
+void launch_rows_select(const uint32_t* S, int64_t nrows, uint64_t cap, uint32_t* tile_cnt, unsigned long long* info,
+                        uint32_t* rows, hipStream_t s);
+// every table entry's column gathered at the kept rows (rows null: rows 0 .. keep - 1) in one launch
+void launch_rows_gather(const RowsCol* d_cols, int ncols, const uint32_t* rows, int64_t keep, hipStream_t s);
+// m.tile_off = per-tile value counts scanned to offsets, info[0] = values of the kept rows
+void launch_rows_mv_len(const RowsMv& m, unsigned long long* info, hipStream_t s);
+void launch_rows_mv_copy(const RowsMv& m, hipStream_t s);
 // Row predicate of a filter on a numeric column: the reference evaluates it per row as a post-filter
 // (QueryableIndexStorageAdapter.makeCursors :244-260 -> FilteredOffset.java:40-105) through the
 // column's ValueMatcher ({Long,Float,Double}ValueMatcherColumnSelectorStrategy, the filters'

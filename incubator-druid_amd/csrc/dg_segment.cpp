@@ -1212,6 +1212,12 @@ int load_segment(Context* ctx, const char* dir, Segment** out) {
     Slice s = index_drd;
     GI cols, dims;
     if (!gi_read(s, &cols) || !gi_read(s, &dims) || s.left() < 16) return set_error(DG_ERR_FORMAT, "bad index.drd");
+    for (int32_t i = 0; i < dims.n; ++i) {
+      const uint8_t* p;
+      const int32_t len = dims.get(i, &p);
+      if (len <= 0) continue;  // (attach never depended on this list: an unreadable name is left out)
+      seg->dims.emplace_back(reinterpret_cast<const char*>(p), (size_t)len);
+    }
     seg->istart = be64(s.p);
     seg->iend = be64(s.p + 8);
     s.p += 16;
@@ -1402,6 +1408,7 @@ int segment_from_rows(Context* ctx, int64_t nrows, const int64_t* ts, int64_t is
       return set_error(DG_ERR_ARG, "%s: column type %d", rc_.name, rc_.type);
     }
     if (rc) return rc;
+    if (c->type == DG_COL_STRING) seg->dims.push_back(c->name);
     add(std::move(c));
   }
   if (nrows) {

@@ -1069,8 +1069,102 @@ class SearchQuery(BaseQuery):
         return js
 
 
+SCAN_RESULT_FORMATS = ("list", "compactedList")
+SCAN_LEGACY_TIMESTAMP = "timestamp"  # ScanQueryEngine.LEGACY_TIMESTAMP_KEY
+SCAN_TIME_COLUMN = "__time"
+
+
+@dataclass
+class ScanQuery(BaseQuery):
+    """ScanQuery (query/scan/ScanQuery.java:53-77): the rows themselves. ``resultFormat`` list (default) or
+    compactedList; ``batchSize`` 0 reads as 20480, ``limit`` 0 as unlimited (:70-71), negative values are
+    IllegalArgumentExceptions (:72-73). Never descending (the constructor passes false, :67). ``legacy``
+    None reads as ScanQueryConfig's default, false (withNonNullLegacy, :137-140)."""
+    virtualColumns: Any = None
+    resultFormat: Optional[str] = None
+    batchSize: int = 0
+    limit: int = 0
+    columns: Optional[List[str]] = None
+    legacy: Optional[bool] = None
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.aggregations:
+            raise ValueError("a scan query has no aggregations")
+        if not self.granularity.is_all:
+            raise ValueError("a scan query has no granularity (its cursor is at ALL, ScanQueryEngine.java:132)")
+        if self.virtualColumns:
+            from ._native import UnsupportedQuery
+            raise UnsupportedQuery(2, "virtual columns are out of scope")
+        self.virtualColumns = []
+        self.resultFormat = "list" if self.resultFormat is None else str(self.resultFormat)
+        if self.resultFormat == "valueVector":
+            # the reference refuses it itself (ScanQueryEngine.java:186-188: UOE)
+            from ._native import UnsupportedQuery
+            raise UnsupportedQuery(2, "resultFormat[valueVector] is not supported")
+        if self.resultFormat not in SCAN_RESULT_FORMATS:
+            raise ValueError(f"resultFormat[{self.resultFormat}] is not supported")
+        self.batchSize = int(self.batchSize or 0)
+        self.limit = int(self.limit or 0)
+        if self.batchSize == 0:
+            self.batchSize = 4096 * 5
+        if self.batchSize <= 0:
+            raise ValueError("batchSize must be greater than 0")
+        if self.limit < 0:
+            raise ValueError("limit must be greater than 0")
+        self.columns = [str(c) for c in (self.columns or [])]
+        self.legacy = bool(self.legacy) if self.legacy is not None else False
+
+    @property
+    def row_limit(self) -> Optional[int]:
+        """None = unlimited (limit 0 reads as Long.MAX_VALUE)."""
+        return self.limit if self.limit > 0 else None
+
+    def column_list(self, dimensions: Sequence[str], metrics: Sequence[str]) -> List[str]:
+        """The result's column list for one segment (ScanQueryEngine.java:85-113): ``columns`` exactly
+        (legacy: ``timestamp`` first when absent), or __time (legacy: ``timestamp``) followed by the
+        segment's dimensions and metrics, without duplicates."""
+        if self.columns:
+            out = list(self.columns)
+            if self.legacy and SCAN_LEGACY_TIMESTAMP not in out:
+                out.insert(0, SCAN_LEGACY_TIMESTAMP)
+            return out
+        out = []
+        for c in [SCAN_LEGACY_TIMESTAMP if self.legacy else SCAN_TIME_COLUMN, *dimensions, *metrics]:
+            if c not in out:
+                out.append(c)
+        if self.legacy and SCAN_TIME_COLUMN in out:
+            out.remove(SCAN_TIME_COLUMN)
+        return out
+
+    def to_json(self):
+        js = self._base_json("scan")
+        js.pop("aggregations", None)
+        js.pop("granularity", None)
+        js.update({"virtualColumns": [], "resultFormat": self.resultFormat, "batchSize": self.batchSize,
+                   "limit": self.limit, "columns": list(self.columns), "legacy": self.legacy})
+        return js
+
+
+@dataclass
+class ScanResultValue:
+    """ScanResultValue (query/scan/ScanResultValue.java): one batch of one segment's rows. ``events``: a
+    list of dicts (list) or of lists in ``columns`` order (compactedList)."""
+    segmentId: str
+    columns: List[str]
+    events: List[Any]
+
+    def to_json(self):
+        return {"segmentId": self.segmentId, "columns": list(self.columns), "events": self.events}
+
+
 def query_from_json(js: Dict[str, Any]):
     qt = js["queryType"]
+    if qt == "scan":
+        return ScanQuery(dataSource=js.get("dataSource", "ds"), intervals=js["intervals"], filter=js.get("filter"),
+                         context=js.get("context", {}) or {}, virtualColumns=js.get("virtualColumns"),
+                         resultFormat=js.get("resultFormat"), batchSize=int(js.get("batchSize", 0) or 0),
+                         limit=int(js.get("limit", 0) or 0), columns=js.get("columns"), legacy=js.get("legacy"))
     common = dict(dataSource=js.get("dataSource", "ds"), intervals=js["intervals"],
                   granularity=js.get("granularity", "all"), filter=js.get("filter"),
                   aggregations=js.get("aggregations", []), context=js.get("context", {}) or {})

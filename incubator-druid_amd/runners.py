@@ -17,6 +17,11 @@ Mirrors the reference's per-segment runner + merge structure:
   GPU (dg_search_run), the limit logic of SearchQueryRunner.run (SearchQueryRunner.java:207-260) over them,
   merged by SearchBinaryFn (SearchBinaryFn.java:53-117).
 
+* ``ScanQueryRunnerFactory`` (query/scan/ScanQueryRunnerFactory.java:64-96): the selected rows' column
+  values gathered on the GPU (dg_rows_run) into a resident rowset, cut on the host into ScanResultValue
+  batches (ScanQueryEngine.java:162-236); the merged runner concatenates the segments' batches under one
+  running count.
+
 Segments that share a device are executed as ONE batched native call (all their rows in one
 launch sequence); results are still kept per segment and merged exactly like the reference merges
 per-segment runners. Cross-device / cross-rank merging is in distributed.py.
@@ -1453,6 +1458,175 @@ def run_search(segments: Sequence[GpuSegment], query: Q.SearchQuery, stats: Opti
 
 
 # ----------------------------------------------------------------------------------------------
+# scan
+# ----------------------------------------------------------------------------------------------
+def scan_native_column(column: str, legacy: bool) -> str:
+    """The segment column a result column reads: legacy ``timestamp`` is __time (ScanQueryEngine.java:152-154)."""
+    return Q.SCAN_TIME_COLUMN if legacy and column == Q.SCAN_LEGACY_TIMESTAMP else column
+
+
+def scan_segment_columns(seg: GpuSegment, query: Q.ScanQuery) -> List[str]:
+    """The column list of one segment's batches (ScanQueryEngine.java:85-113): the dimensions are
+    getAvailableDimensions, the metrics every other column in the segment's column order."""
+    if query.columns:
+        return query.column_list([], [])
+    dims = [d for d in seg.dimensions() if d != Q.SCAN_TIME_COLUMN]
+    mets = [c for c in seg.columns() if c != Q.SCAN_TIME_COLUMN and c not in dims]
+    return query.column_list(dims, mets)
+
+
+def scan_events(columns: Sequence[str], arrays: Dict[str, object], dictionaries: Dict[str, Sequence[Optional[str]]],
+                legacy: bool, compacted: bool = False, n: Optional[int] = None) -> List:
+    """One batch's events from its columns (getColumnValue, ScanQueryEngine.java:238-250). arrays[column]:
+    None for a column the segment lacks (null in every row), an int64 / float32 / float64 array, an int32
+    array of dictionary ids (dictionaries[column] resolves them, None for the empty string), or (ids,
+    offsets) for a multi-value column (DimensionSelector.defaultGetObject: null for an empty row, the value
+    of a one-element row, else the list). In legacy mode ``timestamp`` holds __time and is shown as a UTC
+    ISO instant. Returns dicts in column order (list) or lists (compactedList)."""
+    cols: List[List] = []
+    for c in columns:
+        a = arrays.get(c)
+        if a is None:
+            cols.append(None)
+            continue
+        if isinstance(a, tuple):
+            ids, offs = a
+            d = dictionaries[c]
+            vals = [d[i] for i in ids.tolist()]
+            o = [int(x) for x in offs]
+            col = []
+            for k in range(len(o) - 1):
+                row = vals[o[k]:o[k + 1]]
+                col.append(None if not row else row[0] if len(row) == 1 else row)
+        elif legacy and c == Q.SCAN_LEGACY_TIMESTAMP:
+            col = [Q.format_time(int(t)) for t in a.tolist()]
+        elif c in dictionaries and a.dtype == np.int32:
+            d = dictionaries[c]
+            col = [d[i] for i in a.tolist()]
+        else:
+            col = a.astype(np.float64).tolist() if a.dtype == np.float32 else a.tolist()  # (float32 widens exactly)
+        if n is None:
+            n = len(col)
+        cols.append(col)
+    n = n or 0
+    cols = [c if c is not None else [None] * n for c in cols]
+    if compacted:
+        return [list(r) for r in zip(*cols)] if cols else [[] for _ in range(n)]
+    names = list(columns)
+    return [dict(zip(names, r)) for r in zip(*cols)] if cols else [{} for _ in range(n)]
+
+
+def scan_batches(rowset, seg_ids: Sequence[str], seg_columns: Sequence[Sequence[str]],
+                 native_index: Sequence[Sequence[int]], dictionaries, query: Q.ScanQuery) -> List[Q.ScanResultValue]:
+    """The rowset cut into ScanResultValue batches of at most batchSize rows, segment by segment (a batch
+    never spans segments, ScanQueryEngine.java:162-236); a segment without kept rows yields none.
+    rowset: rows(seg) and fetch(seg, col, start, count) -> (values, offsets); native_index[s][k]: the rowset
+    column of seg_columns[s][k]; dictionaries(s, column) -> the segment's dictionary."""
+    out: List[Q.ScanResultValue] = []
+    compacted = query.resultFormat == "compactedList"
+    for s, sid in enumerate(seg_ids):
+        rows = rowset.rows(s)
+        cols = list(seg_columns[s])
+        for start in range(0, rows, query.batchSize):
+            count = min(query.batchSize, rows - start)
+            arrays, dicts = {}, {}
+            for c, x in zip(cols, native_index[s]):
+                vals, offs = rowset.fetch(s, x, start, count)
+                if vals is None:
+                    arrays[c] = None
+                    continue
+                arrays[c] = vals if offs is None else (vals, offs)
+                if vals.dtype == np.int32:
+                    dicts[c] = dictionaries(s, c)
+            out.append(Q.ScanResultValue(sid, cols, scan_events(cols, arrays, dicts, query.legacy, compacted, count)))
+    return out
+
+
+def scan_rows(segments: Sequence[GpuSegment], columns: Sequence[str], query: Q.ScanQuery, limit: Optional[int],
+              stats: Optional[RunStats] = None, cancel: Optional[ctypes.c_int32] = None) -> "N.RowSet":
+    """One dg_rows_run over segments of one context: the first ``limit`` selected rows (None: all) of the
+    segments in order, the named segment columns gathered into a resident rowset."""
+    scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
+    names = (ctypes.c_char_p * max(len(columns), 1))(*[c.encode("utf-8") for c in columns])
+    spec = N.dg_rows(names, len(columns), int(limit) if limit is not None else 0)
+    h = ctypes.c_void_p()
+    m = N.dg_metrics()
+    N.check(N.lib().dg_rows_run(_handles(segments), len(segments), ctypes.byref(scan), ctypes.byref(spec),
+                                ctypes.byref(h), ctypes.byref(m)))
+    if stats is not None:
+        stats.add(m)
+    del keep
+    return N.RowSet(h, len(segments), len(columns))
+
+
+def _consecutive_by_context(segments: Sequence[GpuSegment]) -> List[List[int]]:
+    """Maximal runs of consecutive segments on one context (scan results keep the segment order)."""
+    runs: List[List[int]] = []
+    for i, s in enumerate(segments):
+        if runs and segments[runs[-1][-1]].context is s.context:
+            runs[-1].append(i)
+        else:
+            runs.append([i])
+    return runs
+
+
+def _scan_run(segs: Sequence[GpuSegment], query: Q.ScanQuery, limit: Optional[int], stats, cancel):
+    """(rowset, batches-builder arguments) of one native call."""
+    seg_columns = [scan_segment_columns(s, query) for s in segs]
+    native: List[str] = []
+    for cols in seg_columns:
+        for c in cols:
+            nc = scan_native_column(c, query.legacy)
+            if nc not in native:
+                native.append(nc)
+    index = [[native.index(scan_native_column(c, query.legacy)) for c in cols] for cols in seg_columns]
+    rowset = scan_rows(segs, native, query, limit, stats, cancel)
+    return rowset, seg_columns, index
+
+
+def run_scan(segments: Sequence[GpuSegment], query: Q.ScanQuery, stats: Optional[RunStats] = None,
+             cancel: Optional[ctypes.c_int32] = None, rows_fn=None) -> List[Q.ScanResultValue]:
+    """ScanQueryRunnerFactory.mergeRunners(...).run (ScanQueryRunnerFactory.java:64-96): the segments'
+    batches concatenated in runner order under one running count (the response context's, ScanQueryEngine
+    .java:68-73,:125): one native call per run of consecutive segments on one context, each with the limit
+    that is left; a run reached once the limit is full is not started. rows_fn (tests): stands in for
+    _scan_run."""
+    rows_fn = rows_fn or _scan_run
+    out: List[Q.ScanResultValue] = []
+    remaining = query.row_limit
+    for idx in _consecutive_by_context(segments):
+        if remaining is not None and remaining <= 0:
+            break
+        segs = [segments[i] for i in idx]
+        rowset, seg_columns, index = rows_fn(segs, query, remaining, stats, cancel)
+        try:
+            out.extend(scan_batches(rowset, [s.identifier for s in segs], seg_columns, index,
+                                    lambda s, c: segs[s].dictionary(scan_native_column(c, query.legacy)), query))
+            if remaining is not None:
+                remaining -= rowset.rows(-1)
+        finally:
+            rowset.close()
+    return out
+
+
+def merge_scan(query: Q.ScanQuery, per_segment: List[List[Q.ScanResultValue]]) -> List[Q.ScanResultValue]:
+    """ScanQueryQueryToolChest.mergeResults over separately run runners: concatenation in runner order,
+    cut at the limit by ScanQueryLimitRowIterator (the batch that crosses it keeps its first events)."""
+    out: List[Q.ScanResultValue] = []
+    remaining = query.row_limit
+    for batches in per_segment:
+        for b in batches:
+            if remaining is not None:
+                if remaining <= 0:
+                    return out
+                if len(b.events) > remaining:
+                    b = Q.ScanResultValue(b.segmentId, b.columns, b.events[:remaining])
+                remaining -= len(b.events)
+            out.append(b)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # factories (QueryRunnerFactory surface)
 # ----------------------------------------------------------------------------------------------
 def exact_granularity(query, segments: Sequence[GpuSegment]):
@@ -1609,8 +1783,23 @@ class SearchQueryRunnerFactory(TimeseriesQueryRunnerFactory):
         return run_search(segments, query, stats)
 
 
+class ScanQueryRunnerFactory(TimeseriesQueryRunnerFactory):
+    """ScanQueryRunnerFactory (query/scan/ScanQueryRunnerFactory.java:64-96): createRunner(segment) runs one
+    segment under the whole limit; the merged runner concatenates the segments' batches and shares the
+    running count between them."""
+    toolchest = _ToolChest(merge_scan)
+
+    @staticmethod
+    def per_segment(segments, query, stats=None):
+        return [run_scan([s], query, stats) for s in segments]
+
+    def run_merged(self, segments, query, stats=None):
+        return run_scan(segments, query, stats)
+
+
 FACTORIES = {Q.TimeseriesQuery: TimeseriesQueryRunnerFactory(), Q.TopNQuery: TopNQueryRunnerFactory(),
-             Q.GroupByQuery: GroupByQueryRunnerFactory(), Q.SearchQuery: SearchQueryRunnerFactory()}
+             Q.GroupByQuery: GroupByQueryRunnerFactory(), Q.SearchQuery: SearchQueryRunnerFactory(),
+             Q.ScanQuery: ScanQueryRunnerFactory()}
 
 
 def run_query(query, segments: Sequence[GpuSegment], stats: Optional[RunStats] = None):

@@ -87,6 +87,13 @@ class GpuSegment:
         L = N.lib()
         return [L.dg_segment_column_name(self.handle, i).decode() for i in range(L.dg_segment_num_columns(self.handle))]
 
+    def dimensions(self) -> List[str]:
+        """StorageAdapter.getAvailableDimensions: index.drd's dimension list (a segment from rows: its
+        string columns in the order given)."""
+        L = N.lib()
+        return [L.dg_segment_dimension_name(self.handle, i).decode()
+                for i in range(L.dg_segment_num_dimensions(self.handle))]
+
     def column_type(self, name: str) -> int:
         t = self._types.get(name)
         if t is None:
