@@ -714,6 +714,11 @@ int dg_debug_lz4_classify(const uint8_t* block, int32_t len, int32_t* kind);
 #define DG_PROBE_HOST_JOIN 10
 int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t iters, double* ms);
 
+/* Where the first radix pass's digit totals of the context's last groupBy call came from: *source = 0
+ * the histogram kernel over the call's elements (or no sort ran), 1 the segments' cached per-value row
+ * counts (built by an earlier eligible groupBy over the same segments and last dimension). */
+int dg_debug_groupby_totals_source(dg_context* ctx, int32_t* source);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,7 +177,7 @@ EXPORTS = [
     "dg_debug_lz4_classify", "dg_host_alloc", "dg_host_free", "dg_set_phase_timing", "dg_debug_probe",
     "dg_groupby_run_opts", "dg_result_grouper_info", "dg_search_run",
     "dg_rows_run", "dg_rowset_rows", "dg_rowset_column_info", "dg_rowset_fetch", "dg_rowset_release",
-    "dg_segment_num_dimensions", "dg_segment_dimension_name",
+    "dg_segment_num_dimensions", "dg_segment_dimension_name", "dg_debug_groupby_totals_source",
 ]
 
 _lib = None
@@ -260,6 +260,7 @@ def lib():
         "dg_set_phase_timing": (ctypes.c_int, [ctypes.c_int32]),
         "dg_debug_probe": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                           P(ctypes.c_double)]),
+        "dg_debug_groupby_totals_source": (ctypes.c_int, [vp, P(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)

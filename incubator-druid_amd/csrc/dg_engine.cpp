@@ -226,7 +226,8 @@ struct CallScratch {
   Pool host;
   UpPool up;
   // per-call device error word (bit 0: corrupt LZ4 block, bit 1: corrupt Roaring bitmap, bit 2:
-  // corrupt multi-value row lists, bit 3 = kErrTableFull: the hash grouper's table is full), read once
+  // corrupt multi-value row lists, bit 3 = kErrTableFull: the hash grouper's table is full, bit 4 =
+  // kErrDictId: a dictionary id outside its dictionary while counting a column's values), read once
   // at the call's final synchronisation instead of after every kernel
   int32_t* d_err = nullptr;
   int32_t* h_err = nullptr;
@@ -404,9 +405,10 @@ static int finish_call(CallScratch* cs, hipStream_t st) {
   DG_HIP(take_launch_error());
   if (cs->d_err && (*cs->h_err & kErrTableFull)) return set_error(DG_ERR_TABLE_FULL, "groupBy hash table full");
   if (cs->d_err && *cs->h_err)
-    return set_error(DG_ERR_FORMAT, (*cs->h_err & 1)   ? "corrupt LZ4 block"
-                                    : (*cs->h_err & 4) ? "corrupt multi-value row lists"
-                                                       : "corrupt Roaring bitmap");
+    return set_error(DG_ERR_FORMAT, (*cs->h_err & 1)            ? "corrupt LZ4 block"
+                                    : (*cs->h_err & 4)          ? "corrupt multi-value row lists"
+                                    : (*cs->h_err & kErrDictId) ? "dictionary id outside its dictionary"
+                                                                : "corrupt Roaring bitmap");
   return DG_OK;
 }
 
@@ -2311,8 +2313,10 @@ static bool has_float_sum(const AggPlan& plan) {
 // device buffers of a sort-based grouping of at most `cap` rows with keys of key_bits bits (call
 // scratch): one 8-byte word per element [key | row ref] when both fit, else keys + a u32 ref array.
 // ref_bits >= 0: the references are not element indices but values of that many bits (hash table positions)
+// one_clear: the sort's and the reduce's control memory in the one-clear layout (SortBufs::ctl), for a
+// caller that issues launch_sort_ctl_clear once; otherwise every pass and the reduce clear their own
 static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bits, int pw, SortBufs* sb,
-                     int ref_bits = -1) {
+                     int ref_bits = -1, bool one_clear = false) {
   memset(sb, 0, sizeof *sb);
   sb->cap = cap;
   sb->ntiles_sort = sort_tiles(cap);
@@ -2331,12 +2335,19 @@ static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bi
     if (!sb->payload) return set_error(DG_ERR_OOM, "payload of %lld rows", (long long)cap);
   }
   sb->tile_cnt = dev_take<uint32_t>(cs, (size_t)std::max(ntiles_keygen, 1));
+  sb->run_cnt = dev_take<uint32_t>(cs, (size_t)sb->ntiles_sort);
+  if (one_clear) {
+    const size_t bytes = sort_ctl_bytes(sb, key_bits);
+    uint8_t* ctl = dev_take<uint8_t>(cs, bytes);
+    if (!sb->tile_cnt || !sb->run_cnt || !ctl) return set_error(DG_ERR_OOM, "sort tables");
+    sort_ctl_bind(sb, key_bits, ctl, bytes);
+    return DG_OK;
+  }
   sb->n = dev_take<uint32_t>(cs, 4);
   sb->lb_status = dev_take<uint64_t>(cs, (size_t)kMaxBins * sb->ntiles_sort);
   // per-pass digit totals + tile counters (radix_passes)
   // + one tile counter for the groupBy reduce's look-back
   sb->bin_total = dev_take<uint32_t>(cs, (size_t)kMaxBins * kRsMaxPasses + kRsMaxPasses + 1);
-  sb->run_cnt = dev_take<uint32_t>(cs, (size_t)sb->ntiles_sort);
   if (!sb->tile_cnt || !sb->n || !sb->lb_status || !sb->bin_total || !sb->run_cnt) return set_error(DG_ERR_OOM, "sort tables");
   return DG_OK;
 }
@@ -4210,6 +4221,7 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   if (rc) return rc;
   CallGuard g(ctx);
   CallScratch* cs = g.cs;
+  ctx->gb_totals_source = 0;
   Interrupt intr(q, t0);
   cs->intr = &intr;
   hipStream_t st = ctx->stream;
@@ -4279,9 +4291,11 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   if (row_total >= (1ll << 32)) return set_error(DG_ERR_UNSUPPORTED, "%lld rows in one call (row refs are 32-bit)", (long long)row_total);
   SortBufs sb;
   if (!any_multi) {
-    rc = sort_bufs(cs, row_total, std::max(ntiles_rows, 1), key_bits, na, &sb);
+    // (the sort's control memory is cleared once, here, ahead of the decodes: launch_sort_ctl_clear)
+    rc = sort_bufs(cs, row_total, std::max(ntiles_rows, 1), key_bits, na, &sb, -1, true);
     if (rc) return rc;
     sb.row_refs = 1;
+    launch_sort_ctl_clear(&sb, st);
   }
   std::vector<const unsigned long long*> counts(n, nullptr);
   DecodeBatch db, db_side;  // db_side: payload columns decoded in place (side stream)
@@ -4390,8 +4404,9 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   if (any_multi) {  // rows explode into one element per grouping: count them first to size the sort
     rc = count_elements(cs, d_jobs, d_tile, ntiles, &total, st);
     if (rc) return rc;
-    rc = sort_bufs(cs, total, ntiles, key_bits, na, &sb);
+    rc = sort_bufs(cs, total, ntiles, key_bits, na, &sb, -1, true);
     if (rc) return rc;
+    launch_sort_ctl_clear(&sb, st);
   }
   // The grouper (dg_groupby_opts): the hash table is sized for max_groups = the limit, capped at the
   // call's elements and at the key space. Not eligible (the sort runs, same result): a floatSum plan
@@ -4416,8 +4431,6 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   }
   uint32_t* h_n = host_take<uint32_t>(cs, 4);
   if (!h_n) return set_error(DG_ERR_OOM, "groupBy counters");
-  DG_FLUSH(cs, st);
-  phase_event(ctx->ev[3], st);
   // every row an element (no filter, no multi-value dimension, every row's time inside the cursor's
   // interval — no time view, or the attach-time block bounds of __time inside it — and no floatSum
   // pass, which reads the per-tile counts): the keygen needs no count pass (DG_GB_COUNT=1: count anyway)
@@ -4434,6 +4447,74 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   };
   bool rows_elems = !any_multi && !has_float_sum(plan) && !env_on("DG_GB_COUNT");
   for (int i = 0; i < n && rows_elems; ++i) rows_elems = !cur[i].any || all_rows_in(i);
+  // The first sort pass's digit totals from the segments' value counts (Column::vcnt, CountTotals)
+  // instead of a read of the elements (k_rs_hist0): the sort grouper over a rows_elems call whose first
+  // digit lies wholly inside the lowest key field, the last dimension's, single-value (or missing) in
+  // every segment. Both are query-independent: the counts are a property of the immutable segment (what
+  // its per-value bitmap index stores), the maps are the cached merged dictionary's. A call that finds
+  // a segment's counts missing builds them from its decoded ids and keeps k_rs_hist0 itself; they
+  // become ready at the end of that call (below), so wrong totals can never reach the scatter.
+  // DG_NO_COUNT_TOTALS=1: k_rs_hist0 always (same-box A/B and tests).
+  bool count_totals = false;
+  CountTotals ctot{};
+  std::vector<int> vc_build;  // segments whose last dimension's counts this call builds
+  unsigned long long *d_vsum = nullptr, *h_vsum = nullptr;
+  const int fd_bits = radix_first_digit_bits(key_bits);
+  if (rows_elems && !use_hash && ntiles > 0 && total > 0 && nd > 0 && fd_bits > 0 && fd_bits <= lay.dim_bits[nd - 1] &&
+      !env_on("DG_NO_COUNT_TOTALS")) {
+    const int ld = nd - 1;
+    bool ok = true;
+    for (int i = 0; i < n && ok; ++i) {
+      if (!cur[i].any) continue;
+      Column* c = sv[i]->find(gb->dimensions[ld]);
+      if (!c) continue;
+      ok = c->type == DG_COL_STRING && !c->multi_value && !c->vcnt_never && gj[i].dims[ld].kind == VIEW_IDS;
+      bool queued = false;  // (a segment listed twice: one build)
+      for (int k : vc_build) queued |= sv[k]->find(gb->dimensions[ld]) == c;
+      if (ok && !c->vcnt_ready && !queued) vc_build.push_back(i);
+    }
+    if (!ok) vc_build.clear();
+    if (ok && vc_build.empty()) {
+      CountJob* d_cj;
+      CountJob* h_cj = up_take<CountJob>(cs, n, &d_cj, st);
+      if (!h_cj) return set_error(DG_ERR_OOM, "value count table");
+      uint32_t max_card = 1;
+      for (int i = 0; i < n; ++i) {
+        memset(&h_cj[i], 0, sizeof(CountJob));
+        if (!cur[i].any) continue;
+        const Column* c = sv[i]->find(gb->dimensions[ld]);
+        h_cj[i].null_gid = gj[i].null_gid[ld];
+        if (!c) {
+          h_cj[i].nrows = (uint32_t)rows[i];
+          continue;
+        }
+        h_cj[i].counts = c->vcnt.as<uint32_t>();
+        h_cj[i].remap = gj[i].remap[ld];
+        h_cj[i].card = (uint32_t)c->dict.size();
+        max_card = std::max(max_card, h_cj[i].card);
+      }
+      ctot = CountTotals{d_cj, n, lay.dim_shift[ld], max_card, (uint32_t)total};
+      count_totals = true;
+    } else if (ok) {
+      for (int i : vc_build) {
+        Column* c = sv[i]->find(gb->dimensions[ld]);
+        if (!c->vcnt.alloc(4 * std::max<size_t>(c->dict.size(), 1)))
+          return set_error(DG_ERR_OOM, "value counts of %s", gb->dimensions[ld]);
+      }
+      d_vsum = dev_take<unsigned long long>(cs, vc_build.size());
+      h_vsum = host_take<unsigned long long>(cs, vc_build.size());
+      if (!d_vsum || !h_vsum || !call_err(cs, st)) return set_error(DG_ERR_OOM, "value count sums");
+    }
+  }
+  ctx->gb_totals_source = count_totals ? 1 : 0;
+  DG_FLUSH(cs, st);
+  for (size_t k = 0; k < vc_build.size(); ++k) {  // (main stream: the key columns are decoded)
+    const int i = vc_build[k];
+    Column* c = sv[i]->find(gb->dimensions[nd - 1]);
+    launch_value_counts(gj[i].dims[nd - 1], rows[i], (uint32_t)c->dict.size(), c->vcnt.as<uint32_t>(), d_vsum + k, cs->d_err,
+                        st);
+  }
+  phase_event(ctx->ev[3], st);
   // The keygen fused into the first radix pass (launch_gb_sort_generated): the sort grouper over a
   // rows_elems call in row-ref mode with packed words, no time view (the bucket would need __time),
   // every dimension a single-value little-endian id view or missing, and the payload columns decoded
@@ -4484,8 +4565,9 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
                        (long long)tab.max_groups, (long long)tab.capacity);
     if (rc) return rc;
   } else {
-    if (fused_keygen) launch_gb_sort_generated(d_jobs, n, total, &sb, key_bits, st);
-    else launch_radix_sort(&sb, key_bits, st);
+    const CountTotals* ct = count_totals ? &ctot : nullptr;
+    if (fused_keygen) launch_gb_sort_generated(d_jobs, n, total, &sb, key_bits, st, ct);
+    else launch_radix_sort(&sb, key_bits, st, ct);
     phase_event(ctx->ev[6], st);
   }
   DG_CHECK_INTERRUPT(intr);
@@ -4543,10 +4625,24 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   }
   phase_event(ctx->ev[4], st);
   if (!use_hash) DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));  // selected rows, groups
+  if (!vc_build.empty()) DG_HIP(hipMemcpyAsync(h_vsum, d_vsum, 8 * vc_build.size(), hipMemcpyDeviceToHost, st));
   ht.mark("reduce_launched");
   rc = finish_call(cs, st);  // (polls the cancel flag / timeout while the device works)
   if (rc) return rc;
   ht.mark("synced");
+  // the value counts built by this call: ready (and part of the segment's footprint) only now that the
+  // call succeeded and only if they sum to the segment's rows; otherwise never used
+  for (size_t k = 0; k < vc_build.size(); ++k) {
+    Segment* seg = sv[vc_build[k]];
+    Column* c = seg->find(gb->dimensions[nd - 1]);
+    if ((int64_t)h_vsum[k] == seg->nrows) {
+      c->vcnt_ready = true;
+      seg->device_bytes += (int64_t)c->vcnt.n;
+    } else {
+      c->vcnt_never = true;
+      c->vcnt.reset();
+    }
+  }
   const int64_t nsel = h_n[0], ng = use_hash ? (int64_t)h_ctr[0] : (int64_t)h_n[1];
   // bufferGrouperMaxSize holds under either grouper (the hash grouper failed at its insert)
   if (choice.max_groups > 0 && ng > choice.max_groups)
@@ -6109,6 +6205,14 @@ extern "C" int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t i
   }
   hipStreamDestroy(st);
   return rc;
+}
+
+extern "C" int dg_debug_groupby_totals_source(dg_context* c, int32_t* source) {
+  Context* ctx = reinterpret_cast<Context*>(c);
+  if (!ctx || !source) return set_error(DG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *source = ctx->gb_totals_source;
+  return DG_OK;
 }
 
 extern "C" int dg_debug_lz4_classify(const uint8_t* block, int32_t len, int32_t* kind) {

@@ -311,7 +311,20 @@ struct SortBufs {
   uint32_t* run_cnt;      // per sort tile: run heads, then their offsets
   int64_t cap;            // element capacity (rows of the call)
   int ntiles_sort;        // sort tiles of `cap`
+  // One-clear control memory (sort_ctl_bind; the groupBy call): `n`, `bin_total`, a look-back status
+  // region per radix pass and the reduce's own lie in one contiguous region [ctl, ctl + ctl_bytes) that
+  // launch_sort_ctl_clear zeroes with a single memset before the call's decodes, instead of a memset in
+  // front of every pass and three in front of the reduce. lb_status is then null. ctl_clean: what is
+  // still zeroed (kCtlSort: the passes' part, kCtlReduce: the reduce's); each user takes its bit, so
+  // a second sort or reduce over the same buffers clears its part itself, as the unbound layout does.
+  uint8_t* ctl;
+  size_t ctl_bytes;
+  uint64_t* pass_status[8];  // [kRsMaxPasses]
+  uint64_t* red_status;
+  int ctl_key_bits;  // the sort the pass regions were laid out for
+  int ctl_clean;
 };
+constexpr int kCtlSort = 1, kCtlReduce = 2;
 
 // ---------------------------------------------------------------------------------------------
 // Host-side objects
@@ -427,6 +440,14 @@ struct Column {
   // grouped by dictionary-id bin (id >> kTopnIxShift), each with its id's low bits (TopnIx)
   DevBuf tix_perm, tix_lid, tix_base;
   bool tix_ready = false;
+  // value counts (built by the first groupBy whose first sort digit lies in this dimension's key field,
+  // then reused): u32[cardinality], entry v = the segment's rows whose dictionary id is v — what the
+  // per-value bitmap index stores. The sort's first-pass digit totals are summed from them (CountJob).
+  // Ready only after a call that succeeded and whose counts summed to the segment's rows; a mismatch
+  // marks the column never eligible (vcnt_never), so it is not rebuilt by every call.
+  DevBuf vcnt;
+  bool vcnt_ready = false;
+  bool vcnt_never = false;
 };
 
 // Merged dictionary of one dimension over a set of segments (the union of their sorted
@@ -468,6 +489,9 @@ struct Context {
   // context's groupBy calls and their bufferGrouperMaxSize (0: unlimited)
   int32_t grouper = DG_GROUPER_SORT;
   int64_t max_groups = 0;
+  // the last groupBy call's source of its first sort pass's digit totals (dg_debug_groupby_totals_source):
+  // 0 = k_rs_hist0 (or no sort), 1 = the segments' value counts
+  int32_t gb_totals_source = 0;
   std::vector<std::shared_ptr<MergedDict>> dict_cache;  // most recent last
   // device blocks of groupBy results: live (size by pointer) and released for reuse
   std::map<void*, size_t> block_size;
@@ -764,8 +788,42 @@ void launch_gb_count_total(const GbJob* d_jobs, const int32_t* d_tile_job, int n
 // the keygen
 void launch_gb_keygen(const GbJob* d_jobs, const int32_t* d_tile_job, int ntiles, SortBufs* sb, AggPlan plan,
                       hipStream_t s, bool multi = false, int64_t all_rows = -1);
-// stable LSD radix sort of sb->keys/refs[cur] on key bits [0, key_bits)
-void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s);
+// The first pass's digit totals without a read of the elements: when every row of every segment is an
+// element (all_rows) and the first digit's key bits lie inside the lowest key field, a single-value
+// dimension's, the totals are a function of the segments' cached value counts (Column::vcnt) and the
+// merged-dictionary maps. One CountJob per segment of the call; counts null = the segment lacks the
+// dimension (its nrows rows carry null_gid) or has no rows.
+struct CountJob {
+  const uint32_t* counts;  // [card]: rows per dictionary id
+  const int32_t* remap;    // local id -> merged id (null: identity)
+  uint32_t card;
+  uint32_t nrows;          // rows of a segment without the dimension (counts null)
+  int32_t null_gid;
+  int32_t pad;
+};
+struct CountTotals {
+  const CountJob* jobs;  // device
+  int njobs;
+  int dim_shift;  // the field's shift inside the key
+  uint32_t max_card;  // largest dictionary of the jobs (sizes the grid)
+  uint32_t n;     // elements of the call (stored to sb->n[0] by the totals kernel)
+};
+constexpr int32_t kErrDictId = 16;  // bit of the call's device error word: a dictionary id >= its cardinality
+// bits of the first digit of a sort over key_bits key bits (0: no pass)
+int radix_first_digit_bits(int key_bits);
+// counts[v] = rows of `ids` below nrows whose id is v (counts zeroed here); an id >= card is not counted
+// and raises kErrDictId; *sum = the counts' total (64-bit)
+void launch_value_counts(const ColView& ids, int64_t nrows, uint32_t card, uint32_t* counts, unsigned long long* sum,
+                         int32_t* d_err, hipStream_t s);
+// stable LSD radix sort of sb->keys/refs[cur] on key bits [0, key_bits); ct: the first pass's digit
+// totals come from the value counts instead of k_rs_hist0
+void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s, const CountTotals* ct = nullptr);
+// The one-clear control layout of SortBufs (its comment): sort_ctl_bytes = the region's size for a sort
+// of key_bits key bits over sb->cap elements, sort_ctl_bind points n / bin_total / pass_status /
+// red_status into it (lb_status becomes null), launch_sort_ctl_clear zeroes it and marks it clean.
+size_t sort_ctl_bytes(const SortBufs* sb, int key_bits);
+void sort_ctl_bind(SortBufs* sb, int key_bits, void* mem, size_t bytes);
+void launch_sort_ctl_clear(SortBufs* sb, hipStream_t s);
 // The keygen fused into the first radix pass: for a call whose every row is an element in row order
 // (launch_gb_keygen's all_rows case) with no time view, single-value little-endian id views (or
 // missing dimensions) and every payload column decoded in place, the sort word of element e is a
@@ -782,7 +840,8 @@ constexpr int kRsGenMinBlockLog2 = 13;
 bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows);
 void launch_gb_keygen_payload(const GbJob* d_jobs, const int32_t* d_tile_job, int tile0, int ntiles, SortBufs* sb,
                               AggPlan plan, hipStream_t s);
-void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s);
+void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s,
+                              const CountTotals* ct = nullptr);
 // run heads of the sorted keys: sb->run_cnt = per-tile offsets, sb->n[1] = runs
 void launch_run_heads(SortBufs* sb, hipStream_t s);
 // head_pos[g] = first sorted element of run g (after launch_run_heads)

@@ -657,6 +657,82 @@ __global__ __launch_bounds__(kST) void k_rs_hist0(const uint64_t* __restrict__ k
   }
 }
 
+// The first pass's digit totals from the segments' value counts (CountTotals): every row of every job is
+// an element and the digit's key bits [shift, shift + bits) lie inside one single-value dimension's
+// field, so the digit of a row is a function of its dictionary id alone: id v of job j adds counts[v]
+// to the digit of its merged id — the bits k_rs_scatter looks at. A job without the dimension adds its
+// rows to the null value's digit. Also stores the element count (n_ptr[0]).
+__global__ __launch_bounds__(kST) void k_rs_totals_counts(const CountJob* __restrict__ jobs, int njobs, int dim_shift,
+                                                          int shift, int bits, uint32_t* __restrict__ totals,
+                                                          uint32_t* __restrict__ n_ptr, uint32_t n) {
+  __shared__ uint32_t s_h[kMaxBins];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < kMaxBins; i += kST) s_h[i] = 0;
+  __syncthreads();
+  const uint64_t mask = (1ull << bits) - 1;
+  auto digit = [&](uint32_t g) { return (int)((((uint64_t)g << dim_shift) >> shift) & mask); };
+  for (int ji = 0; ji < njobs; ++ji) {
+    const CountJob& j = jobs[ji];
+    if (!j.counts) {
+      if (j.nrows && blockIdx.x == 0 && tid == 0) atomicAdd(&s_h[digit((uint32_t)j.null_gid)], j.nrows);
+      continue;
+    }
+    const uint32_t* cnt = j.counts;
+    const int32_t* rm = j.remap;
+    const uint32_t card = j.card;
+    for (uint32_t v = blockIdx.x * kST + tid; v < card; v += gridDim.x * kST) {
+      const uint32_t c = cnt[v];
+      if (c) atomicAdd(&s_h[digit(rm ? (uint32_t)rm[v] : v)], c);
+    }
+  }
+  __syncthreads();
+  for (int d = tid; d < (1 << bits); d += kST)
+    if (s_h[d]) atomicAdd(&totals[d], s_h[d]);
+  if (blockIdx.x == 0 && tid == 0) n_ptr[0] = n;
+}
+
+// Column::vcnt of one (segment, dimension): rows per dictionary id over the call's decoded id view.
+// Dictionaries of at most kCountLdsCard values count in LDS (each workgroup flushes its non-zero
+// counters once), larger ones with global integer atomics (k_search_hist's pattern).
+constexpr int kCountLdsCard = 8192;
+__global__ __launch_bounds__(256) void k_value_counts(ColView ids, int64_t nrows, uint32_t card,
+                                                      uint32_t* __restrict__ counts, int32_t* __restrict__ err) {
+  __shared__ uint32_t s_cnt[kCountLdsCard];
+  const bool lds = card <= (uint32_t)kCountLdsCard;
+  if (lds) {
+    for (uint32_t i = threadIdx.x; i < card; i += 256) s_cnt[i] = 0;
+    __syncthreads();
+  }
+  bool bad = false;
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * 256) {
+    const uint32_t id = load_id(ids, r);
+    if (id >= card) {
+      bad = true;
+      continue;
+    }
+    if (lds) atomicAdd(&s_cnt[id], 1u);
+    else atomicAdd(counts + id, 1u);
+  }
+  if (lds) {
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < card; i += 256)
+      if (s_cnt[i]) atomicAdd(counts + i, s_cnt[i]);
+  }
+  if (bad) atomicOr(err, kErrDictId);
+}
+
+void launch_value_counts(const ColView& ids, int64_t nrows, uint32_t card, uint32_t* counts, unsigned long long* sum,
+                         int32_t* d_err, hipStream_t s) {
+  if (!zero_async(counts, (size_t)std::max<uint32_t>(card, 1u) * sizeof(uint32_t), s)) return;
+  if (nrows > 0 && card > 0) {
+    const int64_t tiles = (nrows + 255) / 256;
+    const int64_t cap = card <= (uint32_t)kCountLdsCard ? 512 : 4096;
+    hipLaunchKernelGGL(k_value_counts, dim3((unsigned)std::min<int64_t>(tiles, cap)), dim3(256), 0, s, ids, nrows, card, counts,
+                       d_err);
+  }
+  hipLaunchKernelGGL(k_sum_u64, dim3(1), dim3(1024), 0, s, counts, (int)card, sum);
+}
+
 // lanes of the wave whose digit equals mine (ballot per digit bit), restricted to valid lanes
 __device__ __forceinline__ uint64_t match_digit(uint32_t d, int bits, bool valid) {
   uint64_t m = __ballot(valid);
@@ -865,22 +941,91 @@ __global__ __launch_bounds__(kRsT) void k_rs_scatter(const uint64_t* __restrict_
   }
 }
 
+// digits of a sort over kb key bits: even widths (npass passes of w bits, the last one what is left)
+static void radix_digits(int kb, int* npass, int* w) {
+  *npass = (kb + kMaxDigitBits - 1) / kMaxDigitBits;
+  *w = (kb + *npass - 1) / *npass;
+}
+
+int radix_first_digit_bits(int key_bits) {
+  if (key_bits <= 0) return 0;
+  int npass, w;
+  radix_digits(key_bits, &npass, &w);
+  return std::min(key_bits, w);
+}
+
+// 30-bit look-back counts hold every prefix (n <= cap); DG_SORT_WIDE_STATUS=1: 64-bit words regardless (tests)
+static bool rs_narrow_status(const SortBufs* sb) {
+  const char* wide = getenv("DG_SORT_WIDE_STATUS");
+  return sb->cap < ((int64_t)1 << 30) && !(wide && *wide && *wide != '0');
+}
+static int rs_scatter_tiles(const SortBufs* sb) { return (sb->ntiles_sort + DG_RS_TILE_MUL - 1) / DG_RS_TILE_MUL; }
+constexpr size_t kBinTotalWords = (size_t)kMaxBins * kRsMaxPasses + kRsMaxPasses + 1;  // SortBufs::bin_total + the reduce's counter
+
+// The one-clear layout of a sort of key_bits key bits over sb->cap elements, each part 256-byte aligned:
+// n (4 words) | bin_total | pass 0's status | ... | the reduce's status. mem null: only the size.
+static size_t sort_ctl_layout(SortBufs* sb, int key_bits, uint8_t* mem) {
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t off = 0;
+  if (mem) sb->n = reinterpret_cast<uint32_t*>(mem + off);
+  off += up(4 * sizeof(uint32_t));
+  if (mem) sb->bin_total = reinterpret_cast<uint32_t*>(mem + off);
+  off += up(kBinTotalWords * sizeof(uint32_t));
+  int npass = 0, w = 0;
+  if (key_bits > 0) radix_digits(key_bits, &npass, &w);
+  const size_t word = rs_narrow_status(sb) ? 4 : 8;
+  for (int p = 0; p < kRsMaxPasses; ++p) {
+    if (mem) sb->pass_status[p] = p < npass ? reinterpret_cast<uint64_t*>(mem + off) : nullptr;
+    if (p < npass) off += up(((size_t)1 << std::min(w, key_bits - p * w)) * rs_scatter_tiles(sb) * word);
+  }
+  if (mem) sb->red_status = reinterpret_cast<uint64_t*>(mem + off);
+  off += up((size_t)sb->ntiles_sort * sizeof(uint64_t));
+  return off;
+}
+
+size_t sort_ctl_bytes(const SortBufs* sb, int key_bits) {
+  SortBufs t = *sb;
+  return sort_ctl_layout(&t, key_bits, nullptr);
+}
+
+void sort_ctl_bind(SortBufs* sb, int key_bits, void* mem, size_t bytes) {
+  sb->ctl = static_cast<uint8_t*>(mem);
+  sb->ctl_bytes = bytes;
+  sb->ctl_key_bits = key_bits;
+  sb->ctl_clean = 0;
+  sb->lb_status = nullptr;
+  sort_ctl_layout(sb, key_bits, sb->ctl);
+}
+
+void launch_sort_ctl_clear(SortBufs* sb, hipStream_t s) {
+  if (sb->ctl && zero_async(sb->ctl, sb->ctl_bytes, s)) sb->ctl_clean = kCtlSort | kCtlReduce;
+}
+
 // LSD passes over key bits [lo, hi) of the key field (above the element index bits). gen: the first
 // pass and its digit totals generate their elements from the job table (nothing has written
 // sb->keys[sb->cur]); the later passes read what the pass before them stored, as always.
-static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGen* gen) {
+// Control memory: with the one-clear layout bound and still clean (launch_sort_ctl_clear, a sort over
+// the bits it was laid out for) nothing is cleared here and every pass has its own status region;
+// otherwise the totals and each pass's status are cleared in front of their kernels.
+static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGen* gen, const CountTotals* ct) {
   const int kb = hi - lo;
   if (kb <= 0) return;
-  const int npass = (kb + kMaxDigitBits - 1) / kMaxDigitBits;
-  const int w = (kb + npass - 1) / npass;
-  const int nt = (sb->ntiles_sort + DG_RS_TILE_MUL - 1) / DG_RS_TILE_MUL;  // scatter tiles
+  int npass, w;
+  radix_digits(kb, &npass, &w);
+  const int nt = rs_scatter_tiles(sb);  // scatter tiles
   uint32_t* totals = sb->bin_total;                            // [npass][kMaxBins]
   uint32_t* ctr = sb->bin_total + kRsMaxPasses * kMaxBins;     // [npass] tile counters
-  if (!zero_async(sb->bin_total, ((size_t)kRsMaxPasses * kMaxBins + kRsMaxPasses) * sizeof(uint32_t), s)) return;
+  const bool bound = sb->ctl && lo == 0 && hi == sb->ctl_key_bits;
+  const bool clean = bound && (sb->ctl_clean & kCtlSort);
+  sb->ctl_clean &= ~kCtlSort;
+  if (!clean && !zero_async(sb->bin_total, ((size_t)kRsMaxPasses * kMaxBins + kRsMaxPasses) * sizeof(uint32_t), s)) return;
   const RsGen none{nullptr, 0, 0};
   // the first pass's digit totals from one read of the keys (gen: of the ids); every pass's scatter
   // counts the next pass's digits of the keys it stores
-  if (gen)
+  if (ct) {
+    hipLaunchKernelGGL(k_rs_totals_counts, dim3((unsigned)std::min(std::max((ct->max_card + kST - 1) / kST, 1u), 256u)), dim3(kST),
+                       0, s, ct->jobs, ct->njobs, ct->dim_shift, lo, std::min(kb, w), totals, sb->n, ct->n);
+  } else if (gen)
     hipLaunchKernelGGL(k_rs_hist0<kSrcGen>, dim3(std::min(nt, 4096)), dim3(kST), 0, s, nullptr, sb->n, sb->ref_bits + lo,
                        std::min(kb, w), totals, *gen);
   else
@@ -892,12 +1037,11 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGe
     const int nbits = p + 1 < npass ? std::min(w, hi - off - w) : 0;
     uint32_t* nt_tot = p + 1 < npass ? totals + (size_t)(p + 1) * kMaxBins : nullptr;
     const int in = sb->cur, out = sb->cur ^ 1;
-    // 30-bit counts hold every prefix (n <= cap); DG_SORT_WIDE_STATUS=1: 64-bit words regardless (tests)
-    const char* wide = getenv("DG_SORT_WIDE_STATUS");
-    const bool narrow = sb->cap < ((int64_t)1 << 30) && !(wide && *wide && *wide != '0');
-    if (!zero_async(sb->lb_status, (size_t)(1 << bits) * nt * (narrow ? 4 : 8), s)) return;  // look-back status
-    uint32_t* st32 = reinterpret_cast<uint32_t*>(sb->lb_status);
-    uint64_t* st64 = sb->lb_status;
+    const bool narrow = rs_narrow_status(sb);
+    uint64_t* status = bound ? sb->pass_status[p] : sb->lb_status;  // look-back status
+    if (!clean && !zero_async(status, (size_t)(1 << bits) * nt * (narrow ? 4 : 8), s)) return;
+    uint32_t* st32 = reinterpret_cast<uint32_t*>(status);
+    uint64_t* st64 = status;
     const uint32_t* tp = totals + (size_t)p * kMaxBins;
     if (gen && p == 0 && narrow)
       hipLaunchKernelGGL((k_rs_scatter<false, uint32_t, kSrcGen>), dim3(nt), dim3(kRsT), 0, s, nullptr, nullptr, sb->keys[out],
@@ -921,10 +1065,10 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGe
   }
 }
 
-void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s) {
+void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s, const CountTotals* ct) {
   if (key_bits <= 0) return;
   static_assert(64 / kMaxDigitBits <= kRsMaxPasses, "passes of a 64-bit key");
-  radix_passes(sb, 0, key_bits, s, nullptr);
+  radix_passes(sb, 0, key_bits, s, nullptr, ct);
 }
 
 bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows) {
@@ -932,14 +1076,17 @@ bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows) {
   return key_bits > 0 && !sb->refs[0] && sb->row_refs && rows > 0 && rows <= (int64_t)0xFFFFFFFFll - kRsTile;
 }
 
-void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s) {
-  const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb->n), (int)(uint32_t)rows, 1, s);
-  if (e != hipSuccess) {
-    note_launch_error(e);
-    return;
+void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s,
+                              const CountTotals* ct) {
+  if (!ct) {  // (the totals kernel of the value counts stores the element count itself)
+    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb->n), (int)(uint32_t)rows, 1, s);
+    if (e != hipSuccess) {
+      note_launch_error(e);
+      return;
+    }
   }
   const RsGen gen{d_jobs, njobs, sb->ref_bits};
-  radix_passes(sb, 0, key_bits, s, &gen);
+  radix_passes(sb, 0, key_bits, s, &gen, ct);
 }
 
 // DG_PROBE_SORT: the headline's sort words — [id0 (17 bits) | id1 (17 bits) | element index], the ids
@@ -1341,17 +1488,24 @@ void launch_gb_reduce(SortBufs* sb, AggPlan plan, uint64_t* out_keys, uint64_t* 
   // the look-back status (the sort's, free again) and the tile counter; the group count starts at 0
   // (a separate k_run_count pass + scan for the tile offsets measured the same, same box: 14.17-14.29
   // vs 14.22-14.25 ms per headline step)
+  // (one-clear layout: the reduce's own status region, zeroed with the counter and the group count by
+  // the call's single clear)
   uint32_t* ctr = sb->bin_total + (size_t)kRsMaxPasses * kMaxBins + kRsMaxPasses;
-  if (!zero_async(sb->lb_status, (size_t)nt * sizeof(uint64_t), s)) return;
-  if (!zero_async(ctr, sizeof(uint32_t), s)) return;
-  if (!zero_async(sb->n + 1, sizeof(uint32_t), s)) return;
+  uint64_t* status = sb->ctl ? sb->red_status : sb->lb_status;
+  const bool clean = sb->ctl && (sb->ctl_clean & kCtlReduce);
+  sb->ctl_clean &= ~kCtlReduce;
+  if (!clean) {
+    if (!zero_async(status, (size_t)nt * sizeof(uint64_t), s)) return;
+    if (!zero_async(ctr, sizeof(uint32_t), s)) return;
+    if (!zero_async(sb->n + 1, sizeof(uint32_t), s)) return;
+  }
   if (refs)
     hipLaunchKernelGGL(k_gb_reduce<true>, dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
-                       sb->ref_bits, sb->n, sb->lb_status, ctr, plan, out_keys, out_slots, cap, head_pos,
+                       sb->ref_bits, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
                        carry_g, carry_slots, open_g);
   else
     hipLaunchKernelGGL(k_gb_reduce<false>, dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
-                       sb->ref_bits, sb->n, sb->lb_status, ctr, plan, out_keys, out_slots, cap, head_pos,
+                       sb->ref_bits, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
                        carry_g, carry_slots, open_g);
   const int64_t nw = (int64_t)nt * kRedWaves;  // carry / open slots: one per wave share of a tile
   const unsigned g = (unsigned)((nw + 255) / 256);
