@@ -28,6 +28,10 @@
  *   dg_groupby_run_opts      <- the same under GroupByQueryConfig's forceHashAggregation / bufferGrouperMaxSize
  *                               (query/groupby/GroupByQueryConfig.java:35-40): BufferHashGrouper over ByteBufferHashTable
  *                               (epinephelinae/BufferHashGrouper.java:38-133, ByteBufferHashTable.java:286-327)
+ *   dg_groupby_run_dims      <- the same with DimensionSpec.getOutputType per dimension (query/dimension/
+ *                               DefaultDimensionSpec.java:68-78): LONG columns grouped by value as
+ *                               GroupByStrategyFactory -> LongGroupByColumnSelectorStrategy does
+ *                               (epinephelinae/GroupByQueryEngineV2.java:235-260)
  *   dg_search_run            <- SearchQueryRunnerFactory.createRunner(segment).run: the counting of SearchQueryRunner.run
  *                               (query/search/SearchQueryRunner.java:207-260) under UseIndexesStrategy.getExecutionPlan
  *                               (UseIndexesStrategy.java:66-109): IndexOnlyExecutor.execute (:236-281) over
@@ -509,6 +513,42 @@ typedef struct {
 int dg_groupby_run_opts(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_groupby* g,
                         const dg_groupby_opts* opts /* NULL = defaults */, dg_result** out, dg_metrics* metrics);
 
+/* groupBy with a DimensionSpec output type per dimension (DefaultDimensionSpec.getOutputType,
+ * query/dimension/DefaultDimensionSpec.java:68-78; every Druid SQL GROUP BY over a long column asks for
+ * LONG). dg_groupby_run / dg_groupby_run_opts are this call with every output_type DG_COL_STRING.
+ *
+ * A dimension that is a LONG column in every segment of the call is grouped by its values, as
+ * GroupByQueryEngineV2.GroupByStrategyFactory does through LongGroupByColumnSelectorStrategy
+ * (epinephelinae/GroupByQueryEngineV2.java:235-260). The first such call dictionary-encodes the column on
+ * the device (its distinct values ascending + one id per row) and the segment keeps the encoding
+ * (dg_debug_long_dim_info); the segments' value lists are merged like string dictionaries. The merged
+ * ids, and so the result's rows, are ordered by the output type:
+ *   DG_COL_LONG    ascending numeric order (LongRowBasedKeySerdeHelper = Longs.compare,
+ *                  RowBasedGrouperHelper.java:1389-1437)
+ *   DG_COL_STRING  the rows carry String.valueOf(value) (convertRowTypesToOutputTypes,
+ *                  GroupByQueryEngineV2.java:689-698; DimensionHandlerUtils.convertObjectToString :245-251)
+ *                  and order as strings: "-5" < "10" < "9"
+ * Refused with DG_ERR_UNSUPPORTED before any launch, naming the column: a dimension that is LONG in some
+ * of the call's segments and a string or missing in others, a FLOAT or DOUBLE dimension, output type LONG
+ * on a string (or everywhere missing) column, any other output type. */
+typedef struct {
+  const char* dimension;
+  int32_t output_type; /* DG_COL_STRING | DG_COL_LONG */
+  int32_t reserved;
+} dg_dimension;
+int dg_groupby_run_dims(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_dimension* dims,
+                        int32_t n_dims, const dg_groupby_opts* opts /* NULL = defaults */, dg_result** out,
+                        dg_metrics* metrics);
+/* What dimension `dim` of a groupBy result is: *column_type = DG_COL_STRING | DG_COL_LONG (what the
+ * dimension's ids index: strings, or the longs of dg_result_dim_longs), *output_type as the query asked
+ * (the ValueType convertRowTypesToOutputTypes gives the row's value, GroupByQueryEngineV2.java:689-698).
+ * A dg_merge result has the caller's dictionaries: DG_ERR_ARG. */
+int dg_result_dim_type(const dg_result* res, int32_t dim, int32_t* column_type, int32_t* output_type);
+/* A long dimension's merged dictionary: out[dg_result_dim_cardinality(res, dim)] in merged-id order (the
+ * row's dimension value before convertRowTypesToOutputTypes). A string dimension: DG_ERR_ARG.
+ * dg_result_dim_dictionary of a long dimension gives each value's decimal text (Long.toString). */
+int dg_result_dim_longs(const dg_result* res, int32_t dim, int64_t* out);
+
 typedef struct {
   int32_t grouper;          /* what actually ran */
   int32_t reserved;
@@ -629,7 +669,9 @@ int dg_merge(dg_context* ctx, const dg_keyspace* ks, const uint64_t* d_keys, con
  * outs[t] = key range t of the merged result, resident on targets[t]; concatenated in t order they
  * are the whole merged, ordered result. The outputs fetch like dg_groupby_run results: their
  * dg_result_dim_dictionary is the union dictionary. n_targets == 1: the whole merge on one device.
- * Parts stay valid (the caller releases them). No transport from the caller is needed. */
+ * Parts stay valid (the caller releases them). No transport from the caller is needed.
+ * A part that groups by a long dimension (dg_groupby_run_dims) is DG_ERR_UNSUPPORTED: the dictionary union
+ * compares strings. dg_result_export / dg_merge with the caller's own maps take such results as any other. */
 int dg_groupby_merge_devices(dg_result* const* parts, int32_t n_parts, dg_context* const* targets, int32_t n_targets,
                              dg_result** outs, dg_metrics* metrics);
 
@@ -718,6 +760,14 @@ int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t iters, doubl
  * the histogram kernel over the call's elements (or no sort ran), 1 the segments' cached per-value row
  * counts (built by an earlier eligible groupBy over the same segments and last dimension). */
 int dg_debug_groupby_totals_source(dg_context* ctx, int32_t* source);
+
+/* The cached long-dimension encoding of a LONG column (built by the first dg_groupby_run* that groups by
+ * it; no reference counterpart, the reference reads the long per row): *built = 0 / 1, *cardinality = its
+ * distinct values, *device_bytes = HBM held by the ids (4 B per row) and the value list (8 B per value),
+ * part of dg_segment_device_bytes, *build_ms = device time of the build. Any output may be NULL.
+ * DG_ERR_NOT_FOUND: no such column; DG_ERR_ARG: not a LONG column. */
+int dg_debug_long_dim_info(dg_segment* seg, const char* column, int32_t* built, int64_t* cardinality,
+                           int64_t* device_bytes, double* build_ms);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,10 @@ class dg_groupby(ctypes.Structure):
     _fields_ = [("dimensions", ctypes.POINTER(ctypes.c_char_p)), ("n_dims", ctypes.c_int32)]
 
 
+class dg_dimension(ctypes.Structure):
+    _fields_ = [("dimension", ctypes.c_char_p), ("output_type", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class dg_groupby_opts(ctypes.Structure):
     _fields_ = [("grouper", ctypes.c_int32), ("reserved", ctypes.c_int32), ("max_groups", ctypes.c_int64)]
 
@@ -178,6 +182,7 @@ EXPORTS = [
     "dg_groupby_run_opts", "dg_result_grouper_info", "dg_search_run",
     "dg_rows_run", "dg_rowset_rows", "dg_rowset_column_info", "dg_rowset_fetch", "dg_rowset_release",
     "dg_segment_num_dimensions", "dg_segment_dimension_name", "dg_debug_groupby_totals_source",
+    "dg_groupby_run_dims", "dg_result_dim_type", "dg_result_dim_longs", "dg_debug_long_dim_info",
 ]
 
 _lib = None
@@ -261,6 +266,11 @@ def lib():
         "dg_debug_probe": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                           P(ctypes.c_double)]),
         "dg_debug_groupby_totals_source": (ctypes.c_int, [vp, P(i32)]),
+        "dg_groupby_run_dims": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_dimension), i32, P(dg_groupby_opts), P(vp),
+                                               P(dg_metrics)]),
+        "dg_result_dim_type": (ctypes.c_int, [vp, i32, P(i32), P(i32)]),
+        "dg_result_dim_longs": (ctypes.c_int, [vp, i32, vp]),
+        "dg_debug_long_dim_info": (ctypes.c_int, [vp, cp, P(i32), P(i64), P(i64), P(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)

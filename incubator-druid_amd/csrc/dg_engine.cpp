@@ -4031,21 +4031,250 @@ int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, c
 
 namespace dg {
 
+// What a groupBy dimension is over the call's segments: 0 = a string dimension (a dictionary-encoded
+// string column, missing segments contribute null), 1 = a long dimension (a LONG column in every segment,
+// grouped by value: GroupByQueryEngineV2.GroupByStrategyFactory -> LongGroupByColumnSelectorStrategy,
+// GroupByQueryEngineV2.java:235-260). Everything else is refused before any launch: a column that is
+// LONG in some segments and a string or missing in others (the reference converts through a nil
+// selector there, with other null / 0 merge rules), FLOAT / DOUBLE dimensions (raw-bit keys per segment,
+// Float / Double.compare at the merge), output type LONG on a string column (the reference parses the
+// strings), any other output type.
+static int dim_kind(Segment* const* segs, int n, const char* dim, int32_t out_type, bool* is_long) {
+  *is_long = false;
+  if (out_type != DG_COL_STRING && out_type != DG_COL_LONG)
+    return set_error(DG_ERR_UNSUPPORTED, "groupBy dimension %s: output type %d (STRING and LONG are supported)", dim, out_type);
+  int n_long = 0;
+  for (int i = 0; i < n; ++i) {
+    const Column* c = segs[i]->find(dim);
+    if (!c) continue;
+    if (c->type == DG_COL_FLOAT || c->type == DG_COL_DOUBLE)
+      return set_error(DG_ERR_UNSUPPORTED, "groupBy on %s column %s", c->type == DG_COL_FLOAT ? "FLOAT" : "DOUBLE", dim);
+    if (c->type == DG_COL_LONG) ++n_long;
+    else if (c->type != DG_COL_STRING) return set_error(DG_ERR_UNSUPPORTED, "groupBy on non-string column %s", dim);
+  }
+  if (n_long > 0 && n_long < n)
+    return set_error(DG_ERR_UNSUPPORTED, "groupBy column %s is LONG in %d of the call's %d segments and a string or missing in the others",
+                     dim, n_long, n);
+  if (n_long == 0 && out_type == DG_COL_LONG)
+    return set_error(DG_ERR_UNSUPPORTED, "groupBy dimension %s: output type LONG on a string column", dim);
+  *is_long = n_long > 0;
+  return DG_OK;
+}
+
+// The long-dimension encoding of one (segment, LONG column), built on the device (dg_numdim.hip) by the
+// first groupBy that groups by the column and kept in the Column like its other query-independent
+// indexes (tix_*, vcnt):
+//   1. the column's VIEW_LONG view through the ordinary decode path (any codec / long encoding / a
+//      segment from rows), 2. its min and max, 3. words (v - min), 4. the radix sort over
+//      bits_for(max - min) key bits (none when max == min), 5. run heads counted per tile and scanned,
+//      6. the cardinality read back, nd_vals allocated at exactly that size and filled (run heads + min),
+//      7. nd_ids[r] = lower bound of v[r] in nd_vals; nd_vals read back once.
+// Three waits (min / max, the cardinality, the end): a one-time build. Scratch (the decoded view, the two
+// word buffers, control memory) is the call's and is the caller's again afterwards. The column takes the
+// buffers only when every step succeeded: a failed or interrupted build leaves it without an encoding and
+// the next call builds again. cancel / timeout are checked between the launch groups and polled in the waits.
+static int build_long_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c, hipStream_t st) {
+  if (c->nd_ready) return DG_OK;
+  const int64_t nrows = seg->nrows;
+  if (c->data.total != nrows)
+    return set_error(DG_ERR_FORMAT, "column %s holds %d rows, its segment %lld", c->name.c_str(), c->data.total, (long long)nrows);
+  // (one block of 4-byte ids: the id loaders form a row's byte offset in 32 bits)
+  if (nrows >= (1ll << 30)) return set_error(DG_ERR_UNSUPPORTED, "groupBy on LONG column %s of %lld rows", c->name.c_str(), (long long)nrows);
+  DevBuf ids, vals, ptr;
+  std::vector<int64_t> host;
+  int64_t card = 0;
+  float build_ms = 0;
+  auto interrupted = [&]() { return cs->intr ? cs->intr->check() : DG_OK; };
+  auto body = [&]() -> int {
+    int rc = interrupted();
+    if (rc) return rc;
+    if (nrows == 0) return DG_OK;
+    if (!ids.alloc(((size_t)nrows + 16) * 4) || !ptr.alloc(sizeof(void*)))
+      return set_error(DG_ERR_OOM, "long-dimension ids of %s", c->name.c_str());
+    DG_HIP(hipEventRecord(ctx->ev[6], st));
+    DG_HIP(hipMemsetAsync(ids.p, 0, ids.n, st));
+    DecodeBatch db;
+    ColView v;
+    rc = column_view(c, cs, &db, &v, st);
+    if (rc) return rc;
+    unsigned long long* d_mm;
+    unsigned long long* s_mm = up_take<unsigned long long>(cs, 2, &d_mm, st);
+    unsigned long long* h_mm = host_take<unsigned long long>(cs, 2);
+    if (!s_mm || !h_mm) return set_error(DG_ERR_OOM, "long-dimension scratch");
+    s_mm[0] = ~0ull;
+    s_mm[1] = 0ull;
+    rc = run_decodes(cs, &db, st);
+    if (rc) return rc;
+    DG_FLUSH(cs, st);
+    launch_nd_minmax(v, nrows, d_mm, st);
+    DG_HIP(hipMemcpyAsync(h_mm, d_mm, 16, hipMemcpyDeviceToHost, st));
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    constexpr uint64_t sign = 0x8000000000000000ull;
+    const int64_t vmin = (int64_t)(h_mm[0] ^ sign), vmax = (int64_t)(h_mm[1] ^ sign);
+    if (vmin > vmax) return set_error(DG_ERR_DEVICE, "long-dimension bounds of %s", c->name.c_str());
+    const uint64_t range = (uint64_t)vmax - (uint64_t)vmin;
+    int key_bits = 0;
+    while (key_bits < 64 && (range >> key_bits)) ++key_bits;
+    rc = interrupted();
+    if (rc) return rc;
+    if (key_bits == 0) {  // a constant column: one value, every id 0 (the ids are zeroed), no sort
+      card = 1;
+      host.assign(1, vmin);
+      if (!vals.alloc(8)) return set_error(DG_ERR_OOM, "long-dimension values of %s", c->name.c_str());
+      DG_HIP(hipMemcpy(vals.p, host.data(), 8, hipMemcpyHostToDevice));
+    } else {
+      SortBufs sb;
+      rc = sort_bufs(cs, nrows, 1, key_bits, 0, &sb, 0);  // packed words, no reference bits: the key is the word
+      if (rc) return rc;
+      unsigned long long* d_info = dev_take<unsigned long long>(cs, 1);
+      unsigned long long* h_info = host_take<unsigned long long>(cs, 1);
+      if (!d_info || !h_info) return set_error(DG_ERR_OOM, "long-dimension scratch");
+      launch_nd_words(v, nrows, vmin, sb.keys[0], st);
+      DG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb.n), (int)(uint32_t)nrows, 1, st));
+      launch_radix_sort(&sb, key_bits, st);
+      rc = interrupted();
+      if (rc) return rc;
+      launch_nd_unique_count(sb.keys[sb.cur], nrows, sb.run_cnt, d_info, st);
+      DG_HIP(hipMemcpyAsync(h_info, d_info, 8, hipMemcpyDeviceToHost, st));
+      rc = finish_call(cs, st);
+      if (rc) return rc;
+      card = (int64_t)*h_info;
+      if (card < 1 || card > nrows) return set_error(DG_ERR_DEVICE, "long-dimension cardinality %lld of %s", (long long)card, c->name.c_str());
+      if (!vals.alloc((size_t)card * 8)) return set_error(DG_ERR_OOM, "long-dimension values of %s", c->name.c_str());
+      host.resize((size_t)card);
+      launch_nd_unique_emit(sb.keys[sb.cur], nrows, sb.run_cnt, vmin, vals.as<int64_t>(), card, st);
+      rc = interrupted();
+      if (rc) return rc;
+      launch_nd_encode(v, nrows, vals.as<int64_t>(), (uint32_t)card, ids.as<uint32_t>(), st);
+    }
+    DG_HIP(hipEventRecord(ctx->ev[7], st));
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    if (key_bits) DG_HIP(hipMemcpy(host.data(), vals.p, (size_t)card * 8, hipMemcpyDeviceToHost));
+    const void* p = ids.p;
+    DG_HIP(hipMemcpy(ptr.p, &p, sizeof p, hipMemcpyHostToDevice));
+    DG_HIP(hipEventElapsedTime(&build_ms, ctx->ev[6], ctx->ev[7]));
+    for (int64_t k = 1; k < card; ++k)
+      if (host[k - 1] >= host[k]) return set_error(DG_ERR_DEVICE, "long-dimension values of %s out of order", c->name.c_str());
+    return DG_OK;
+  };
+  const int rc = body();
+  if (rc) {  // (queued kernels still use the buffers freed below)
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  std::swap(c->nd_ids.p, ids.p);
+  std::swap(c->nd_ids.n, ids.n);
+  std::swap(c->nd_vals.p, vals.p);
+  std::swap(c->nd_vals.n, vals.n);
+  std::swap(c->nd_ptr.p, ptr.p);
+  std::swap(c->nd_ptr.n, ptr.n);
+  c->nd_host.swap(host);
+  c->nd_card = card;
+  c->nd_build_ms = build_ms;
+  c->nd_ready = true;
+  seg->device_bytes += (int64_t)(c->nd_ids.n + c->nd_vals.n);
+  return DG_OK;
+}
+
 // Merged dictionary of `dim` over the call's segments: k-way merge of their sorted dictionaries
 // (GenericIndexed STRING_STRATEGY = Java String.compareTo with nulls first), plus each segment's
 // local id -> merged id table in HBM. A segment without the column contributes the null value.
-static int merged_dict(Context* ctx, Segment* const* segs, int n, const std::string& dim, std::shared_ptr<MergedDict>* out) {
+//
+// A long dimension (LONG in every segment, dim_kind): the segments' sorted value lists (Column::nd_host,
+// build_long_dim) merge the same way into MergedDict::longs, ordered by the output type — DG_COL_LONG:
+// ascending, the order LongRowBasedKeySerdeHelper compares grouping keys in (Longs.compare,
+// RowBasedGrouperHelper.java:1389-1437); DG_COL_STRING: the rows carry String.valueOf(value)
+// (convertRowTypesToOutputTypes, GroupByQueryEngineV2.java:689-698) and GroupByMergingQueryRunnerV2
+// (:188-246) merges them through the string key helper, i.e. String.compareTo of the decimal text
+// ("-5" < "10" < "9"; long_text_less). That order's local id -> merged id tables are not monotone; the
+// grouping only needs them to be maps.
+static int merged_dict(Context* ctx, Segment* const* segs, int n, const std::string& dim, int32_t out_type, bool is_long,
+                       std::shared_ptr<MergedDict>* out) {
   std::vector<uint64_t> uids(n);
   for (int i = 0; i < n; ++i) uids[i] = segs[i]->uid;
   for (auto it = ctx->dict_cache.rbegin(); it != ctx->dict_cache.rend(); ++it)
-    if ((*it)->dim == dim && (*it)->uids == uids) {
+    if ((*it)->dim == dim && (*it)->uids == uids && (*it)->out_type == out_type && (*it)->is_long == is_long) {
       *out = *it;
       return DG_OK;
     }
   auto md = std::make_shared<MergedDict>();
   md->uids = uids;
   md->dim = dim;
+  md->out_type = out_type;
+  md->is_long = is_long;
   md->remap.resize(n);
+  if (is_long) {
+    std::vector<const std::vector<int64_t>*> lists(n);
+    for (int i = 0; i < n; ++i) lists[i] = &segs[i]->find(dim)->nd_host;
+    bool same = true;
+    for (int i = 1; i < n && same; ++i) same = lists[i] == lists[0] || *lists[i] == *lists[0];
+    std::vector<int64_t> uni;                   // the union, ascending
+    std::vector<std::vector<int32_t>> host(n);  // local id -> position in the merged list
+    if (same) {
+      uni = *lists[0];
+    } else {
+      struct Cur {
+        int seg;
+        size_t pos;
+      };
+      auto later = [&](const Cur& a, const Cur& b) {  // min-heap on (value, segment)
+        const int64_t x = (*lists[a.seg])[a.pos], y = (*lists[b.seg])[b.pos];
+        return x != y ? x > y : a.seg > b.seg;
+      };
+      std::priority_queue<Cur, std::vector<Cur>, decltype(later)> pq(later);
+      for (int i = 0; i < n; ++i) {
+        host[i].resize(lists[i]->size());
+        if (!lists[i]->empty()) pq.push(Cur{i, 0});
+      }
+      while (!pq.empty()) {
+        Cur c = pq.top();
+        pq.pop();
+        const int64_t v = (*lists[c.seg])[c.pos];
+        if (uni.empty() || uni.back() != v) uni.push_back(v);
+        host[c.seg][c.pos] = (int32_t)uni.size() - 1;
+        if (++c.pos < lists[c.seg]->size()) pq.push(c);
+      }
+    }
+    if (uni.size() >= ((size_t)1 << 31)) return set_error(DG_ERR_UNSUPPORTED, "%zu values of %s", uni.size(), dim.c_str());
+    std::vector<int32_t> rank;  // STRING output: position of the k-th smallest value in decimal-text order
+    if (out_type == DG_COL_STRING) {
+      std::vector<std::pair<LongTextKey, int32_t>> keyed(uni.size());
+      for (size_t k = 0; k < uni.size(); ++k) keyed[k] = {long_text_key(uni[k]), (int32_t)k};
+      std::sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+      rank.resize(uni.size());
+      md->longs.resize(uni.size());
+      bool moved = false;
+      for (size_t k = 0; k < keyed.size(); ++k) {
+        rank[keyed[k].second] = (int32_t)k;
+        md->longs[k] = uni[keyed[k].second];
+        moved |= keyed[k].second != (int32_t)k;
+      }
+      if (!moved) rank.clear();
+    } else {
+      md->longs = uni;
+    }
+    for (int i = 0; i < n; ++i) {
+      if (same && rank.empty()) break;  // identity maps
+      if (same) {
+        host[i] = rank;
+      } else if (!rank.empty()) {
+        for (auto& g : host[i]) g = rank[g];
+      }
+      if (host[i].empty()) continue;
+      bool identity = true;
+      for (size_t k = 0; identity && k < host[i].size(); ++k) identity = host[i][k] == (int32_t)k;
+      if (identity) continue;
+      md->remap[i].reset(new DevBuf());
+      if (!md->remap[i]->alloc(host[i].size() * 4)) return set_error(DG_ERR_OOM, "hipMalloc dictionary map");
+      DG_HIP(hipMemcpy(md->remap[i]->p, host[i].data(), host[i].size() * 4, hipMemcpyHostToDevice));
+    }
+    ctx->dict_cache.push_back(md);
+    if (ctx->dict_cache.size() > 32) ctx->dict_cache.erase(ctx->dict_cache.begin());
+    *out = md;
+    return DG_OK;
+  }
   std::vector<const Column*> cols(n, nullptr);
   bool need_null = false;
   for (int i = 0; i < n; ++i) {
@@ -4192,6 +4421,9 @@ struct ResultDrop {
 };
 using PendingResult = std::unique_ptr<dg_result, ResultDrop>;
 
+static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb,
+                            const int32_t* out_types, const dg_groupby_opts* opts, dg_result** out, dg_metrics* metrics);
+
 extern "C" {
 
 int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb, dg_result** out,
@@ -4201,6 +4433,30 @@ int dg_groupby_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const d
 
 int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb,
                         const dg_groupby_opts* opts, dg_result** out, dg_metrics* metrics) {
+  if (!gb) return set_error(DG_ERR_ARG, "null argument");
+  return groupby_run_impl(segs, n, q, gb, nullptr, opts, out, metrics);  // every output type STRING
+}
+
+int dg_groupby_run_dims(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_dimension* dims, int32_t n_dims,
+                        const dg_groupby_opts* opts, dg_result** out, dg_metrics* metrics) {
+  if (n_dims < 0 || n_dims > kMaxGroupDims)
+    return set_error(DG_ERR_UNSUPPORTED, "%d groupBy dimensions (max %d)", n_dims, kMaxGroupDims);
+  if (n_dims > 0 && !dims) return set_error(DG_ERR_ARG, "null argument");
+  const char* names[kMaxGroupDims] = {};
+  int32_t types[kMaxGroupDims] = {};
+  for (int d = 0; d < n_dims; ++d) {
+    names[d] = dims[d].dimension;
+    types[d] = dims[d].output_type;
+  }
+  const dg_groupby gb{names, n_dims};
+  return groupby_run_impl(segs, n, q, &gb, types, opts, out, metrics);
+}
+
+}  // extern "C"
+
+// out_types: DimensionSpec.getOutputType of every dimension (null: all DG_COL_STRING)
+static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_groupby* gb,
+                            const int32_t* out_types, const dg_groupby_opts* opts, dg_result** out, dg_metrics* metrics) {
   auto t0 = std::chrono::steady_clock::now();
   HostTrace ht;
   Context* ctx;
@@ -4219,19 +4475,39 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   AggPlan plan;
   rc = make_plan(q, &plan);
   if (rc) return rc;
+  std::vector<Segment*> sv(n);
+  for (int i = 0; i < n; ++i) sv[i] = reinterpret_cast<Segment*>(segs[i]);
+  // string or long dimensions (dim_kind; what it refuses is refused here, before any launch)
+  bool dim_long[kMaxGroupDims] = {};
+  for (int d = 0; d < nd; ++d) {
+    if (!gb->dimensions || !gb->dimensions[d]) return set_error(DG_ERR_ARG, "null dimension %d", d);
+    rc = dim_kind(sv.data(), n, gb->dimensions[d], out_types ? out_types[d] : DG_COL_STRING, &dim_long[d]);
+    if (rc) return rc;
+  }
   CallGuard g(ctx);
   CallScratch* cs = g.cs;
   ctx->gb_totals_source = 0;
   Interrupt intr(q, t0);
   cs->intr = &intr;
   hipStream_t st = ctx->stream;
+  // the long dimensions' encodings this call is the first to need (build_long_dim): each build ends with
+  // a wait, after which its scratch is the call's again
+  for (int d = 0; d < nd; ++d) {
+    if (!dim_long[d]) continue;
+    for (int i = 0; i < n; ++i) {
+      Column* c = sv[i]->find(gb->dimensions[d]);
+      if (c->nd_ready) continue;
+      rc = build_long_dim(ctx, cs, sv[i], c, st);
+      if (rc) return rc;
+      cs->reset();
+      cs->intr = &intr;
+    }
+  }
   rc = upload_grain(cs, &gr, st);
   if (rc) return rc;
   dg_metrics m;
   memset(&m, 0, sizeof m);
   const int na = plan.n, rec = na + 1;
-  std::vector<Segment*> sv(n);
-  for (int i = 0; i < n; ++i) sv[i] = reinterpret_cast<Segment*>(segs[i]);
   std::vector<Cursors> cur(n);
   for (int i = 0; i < n; ++i) {
     cur[i] = plan_cursors(sv[i], i, q, gr);
@@ -4240,8 +4516,7 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   // merged dictionaries (GroupByMergingQueryRunnerV2 merges by value; merged ids order like values)
   std::vector<std::shared_ptr<MergedDict>> md(nd);
   for (int d = 0; d < nd; ++d) {
-    if (!gb->dimensions || !gb->dimensions[d]) return set_error(DG_ERR_ARG, "null dimension %d", d);
-    rc = merged_dict(ctx, sv.data(), n, gb->dimensions[d], &md[d]);
+    rc = merged_dict(ctx, sv.data(), n, gb->dimensions[d], out_types ? out_types[d] : DG_COL_STRING, dim_long[d], &md[d]);
     if (rc) return rc;
   }
   // buckets shared by the segments: one index origin (bucket starts are on one period grid)
@@ -4260,7 +4535,7 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   int shift = 0;
   for (int d = nd - 1; d >= 0; --d) {
     lay.dim_shift[d] = shift;
-    lay.dim_bits[d] = bits_for(std::max<int64_t>((int64_t)md[d]->values.size(), 1));
+    lay.dim_bits[d] = bits_for(std::max<int64_t>((int64_t)md[d]->card(), 1));
     shift += lay.dim_bits[d];
   }
   lay.bucket_shift = shift;
@@ -4330,6 +4605,18 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
         rc = multi_view(c, cs, &db, &j.dims[d], &j.moff[d], st);
         if (rc) return rc;
         j.multi = 1;
+        j.remap[d] = md[d]->remap[i] ? md[d]->remap[i]->as<int32_t>() : nullptr;
+      } else if (c && md[d]->is_long) {
+        // the column's cached ids as one block of little-endian 4-byte ids (Column::nd_ids): what the id
+        // loaders and the generated first radix pass read without change
+        if (!c->nd_ready || (!c->nd_ptr.p && seg->nrows > 0))
+          return set_error(DG_ERR_ARG, "long dimension %s has no encoding", c->name.c_str());
+        j.dims[d].blocks = c->nd_ptr.as<const uint8_t*>();
+        j.dims[d].log2_per = kNdLog2Per;
+        j.dims[d].width = 4;
+        j.dims[d].kind = seg->nrows > 0 ? VIEW_IDS : VIEW_ABSENT;
+        j.dims[d].pad = 0;
+        db.bytes += 4 * seg->nrows;
         j.remap[d] = md[d]->remap[i] ? md[d]->remap[i]->as<int32_t>() : nullptr;
       } else if (c) {
         rc = column_view(c, cs, &db, &j.dims[d], st);
@@ -4709,6 +4996,8 @@ int dg_groupby_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, co
   return DG_OK;
 }
 
+extern "C" {
+
 int64_t dg_result_groups(const dg_result* r) { return r ? r->ngroups : -1; }
 
 int dg_result_grouper_info(const dg_result* r, dg_grouper_info* out) {
@@ -4889,6 +5178,18 @@ int dg_result_dim_dictionary(const dg_result* r, int32_t dim, int64_t* offsets, 
   if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
   const MergedDict& d = *r->dicts[dim];
   int64_t t = 0;
+  if (d.is_long) {  // the decimal text of each value (Long.toString), formatted here: the dictionary holds longs
+    for (size_t i = 0; i < d.longs.size(); ++i) {
+      char buf[24];
+      const int len = snprintf(buf, sizeof buf, "%lld", (long long)d.longs[i]);
+      if (offsets) offsets[i] = t;
+      if (bytes) memcpy(bytes + t, buf, (size_t)len);
+      t += len;
+    }
+    if (offsets) offsets[d.longs.size()] = t;
+    if (total) *total = t;
+    return DG_OK;
+  }
   for (size_t i = 0; i < d.values.size(); ++i) {
     if (offsets) offsets[i] = t;
     if (bytes && !d.is_null[i]) memcpy(bytes + t, d.values[i].data(), d.values[i].size());
@@ -5006,7 +5307,25 @@ int dg_result_limit(dg_result* r, const dg_limit* spec) {
 int32_t dg_result_dim_cardinality(const dg_result* r, int32_t dim) {
   if (!r || dim < 0 || dim >= r->ndims) return -1;
   if (r->dicts.empty()) return r->cards[dim];
-  return (int32_t)r->dicts[dim]->values.size();
+  return (int32_t)r->dicts[dim]->card();
+}
+
+int dg_result_dim_type(const dg_result* r, int32_t dim, int32_t* column_type, int32_t* output_type) {
+  if (!r || dim < 0 || dim >= r->ndims) return set_error(DG_ERR_ARG, "dimension index %d", dim);
+  if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
+  if (column_type) *column_type = r->dicts[dim]->is_long ? DG_COL_LONG : DG_COL_STRING;
+  if (output_type) *output_type = r->dicts[dim]->out_type;
+  return DG_OK;
+}
+
+int dg_result_dim_longs(const dg_result* r, int32_t dim, int64_t* out) {
+  if (!r || dim < 0 || dim >= r->ndims) return set_error(DG_ERR_ARG, "dimension index %d", dim);
+  if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
+  const MergedDict& d = *r->dicts[dim];
+  if (!d.is_long) return set_error(DG_ERR_ARG, "dimension %d (%s) is a string dimension", dim, d.dim.c_str());
+  if (!out && !d.longs.empty()) return set_error(DG_ERR_ARG, "null argument");
+  if (!d.longs.empty()) memcpy(out, d.longs.data(), d.longs.size() * 8);
+  return DG_OK;
 }
 
 void dg_result_release(dg_result* r) { delete r; }
@@ -5794,6 +6113,10 @@ int dg_groupby_merge_devices(dg_result* const* parts, int32_t n_parts, dg_contex
     if (r->limited) return set_error(DG_ERR_ARG, "part %d is a limited result (not in key order)", p);
     if (r->dicts.empty() || (int)r->dicts.size() != r->ndims)
       return set_error(DG_ERR_ARG, "part %d is not a dg_groupby_run result", p);
+    for (const auto& pd : r->dicts)  // (the dictionary union below compares strings)
+      if (pd->is_long)
+        return set_error(DG_ERR_UNSUPPORTED, "part %d groups by the long dimension %s: the in-process device merge unions string dictionaries",
+                         p, pd->dim.c_str());
     if (r->ndims != r0->ndims || r->naggs != r0->naggs || r->kinds != r0->kinds || r->period != r0->period ||
         r->bounds != r0->bounds || (!r->period && r->universal != r0->universal))
       return set_error(DG_ERR_ARG, "part %d is not a result of the same query", p);
@@ -6212,6 +6535,21 @@ extern "C" int dg_debug_groupby_totals_source(dg_context* c, int32_t* source) {
   if (!ctx || !source) return set_error(DG_ERR_ARG, "null argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   *source = ctx->gb_totals_source;
+  return DG_OK;
+}
+
+extern "C" int dg_debug_long_dim_info(dg_segment* s, const char* column, int32_t* built, int64_t* cardinality,
+                                      int64_t* device_bytes, double* build_ms) {
+  Segment* seg = reinterpret_cast<Segment*>(s);
+  if (!seg || !column) return set_error(DG_ERR_ARG, "null argument");
+  const Column* c = seg->find(column);
+  if (!c) return set_error(DG_ERR_NOT_FOUND, "no column %s", column);
+  if (c->type != DG_COL_LONG) return set_error(DG_ERR_ARG, "%s is not a LONG column", column);
+  std::lock_guard<std::mutex> g(seg->ctx->mu);
+  if (built) *built = c->nd_ready ? 1 : 0;
+  if (cardinality) *cardinality = c->nd_ready ? c->nd_card : 0;
+  if (device_bytes) *device_bytes = c->nd_ready ? (int64_t)(c->nd_ids.n + c->nd_vals.n) : 0;
+  if (build_ms) *build_ms = c->nd_ready ? c->nd_build_ms : 0.0;
   return DG_OK;
 }
 

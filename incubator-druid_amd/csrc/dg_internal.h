@@ -448,7 +448,18 @@ struct Column {
   DevBuf vcnt;
   bool vcnt_ready = false;
   bool vcnt_never = false;
+  // long-dimension encoding of a LONG column (built on the device by the first groupBy that groups by the
+  // column, then reused; dg_numdim.hip): nd_vals = int64[nd_card], the column's distinct values ascending
+  // (nd_host: its host copy, read back once); nd_ids = uint32[rows], row r's index into nd_vals, viewed by
+  // the groupBy as ONE block of little-endian 4-byte ids (nd_ptr: the one-entry block table in HBM,
+  // log2_per = kNdLog2Per). Ready only after a build that ran to its end.
+  DevBuf nd_vals, nd_ids, nd_ptr;
+  std::vector<int64_t> nd_host;
+  int64_t nd_card = 0;
+  double nd_build_ms = 0;
+  bool nd_ready = false;
 };
+constexpr int kNdLog2Per = 31;  // rows of a segment are int32: every row lies in block 0
 
 // Merged dictionary of one dimension over a set of segments (the union of their sorted
 // dictionaries in Java String order, nulls first) + each segment's local id -> merged id table in
@@ -462,7 +473,42 @@ struct MergedDict {
   std::vector<uint8_t> is_null;
   int32_t null_gid = -1;                        // merged id of null (-1: no null value)
   std::vector<std::unique_ptr<DevBuf>> remap;   // per segment: int32[card] (empty = identity)
+  // A long dimension (the column is LONG in every segment): the merged values are `longs` (values /
+  // is_null stay empty, a long column has no null), in the order of the dimension's output type —
+  // DG_COL_LONG: ascending; DG_COL_STRING: Java String order of their decimal text (long_text_less).
+  bool is_long = false;
+  int32_t out_type = DG_COL_STRING;  // DimensionSpec.getOutputType
+  std::vector<int64_t> longs;
+  size_t card() const { return is_long ? longs.size() : values.size(); }
 };
+
+// Java String.compareTo of String.valueOf(a) and String.valueOf(b) without forming the text: '-' sorts
+// before every digit, so negatives come first; two magnitudes compare as their digit strings do, i.e. as
+// the numbers padded with zeros on the right to 19 digits
+// (a magnitude has at most 19, and 10^19 - 1 fits 64 bits), the shorter first when those are equal.
+struct LongTextKey {
+  int neg;           // 0 for "-…" (sorts first), 1 otherwise
+  uint64_t mag;  // the magnitude's digits followed by zeros up to 19 digits
+  int len;           // digits of the magnitude
+  bool operator<(const LongTextKey& o) const {
+    if (neg != o.neg) return neg < o.neg;
+    if (mag != o.mag) return mag < o.mag;
+    return len < o.len;
+  }
+};
+inline LongTextKey long_text_key(int64_t v) {
+  LongTextKey k;
+  k.neg = v < 0 ? 0 : 1;
+  uint64_t m = v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;  // (|Long.MIN_VALUE| = 2^63 fits)
+  int len = 1;
+  for (uint64_t t = m; t >= 10; t /= 10) ++len;
+  uint64_t a = m;
+  for (int i = len; i < 19; ++i) a *= 10;
+  k.mag = a;
+  k.len = len;
+  return k;
+}
+inline bool long_text_less(int64_t a, int64_t b) { return long_text_key(a) < long_text_key(b); }
 
 struct Context {
   int device = 0;
@@ -659,6 +705,19 @@ void launch_rows_gather(const RowsCol* d_cols, int ncols, const uint32_t* rows, 
 // m.tile_off = per-tile value counts scanned to offsets, info[0] = values of the kept rows
 void launch_rows_mv_len(const RowsMv& m, unsigned long long* info, hipStream_t s);
 void launch_rows_mv_copy(const RowsMv& m, hipStream_t s);
+// ---- long-dimension encoding (dg_numdim.hip; Column::nd_*) ----
+// mm (host-initialised to {~0, 0}): [0] = min, [1] = max of the rows as (value ^ sign) keys
+void launch_nd_minmax(const ColView& v, int64_t nrows, unsigned long long* mm, hipStream_t s);
+// words[r] = (uint64)(v[r] - vmin)
+void launch_nd_words(const ColView& v, int64_t nrows, int64_t vmin, uint64_t* words, hipStream_t s);
+// run heads of the n sorted words: tile_cnt (sort_tiles(n) entries) = the heads per tile of kSortTile,
+// scanned to exclusive offsets; info[0] = their total, the cardinality
+void launch_nd_unique_count(const uint64_t* words, int64_t n, uint32_t* tile_cnt, unsigned long long* info, hipStream_t s);
+// vals[k] = word of the k-th run head + vmin, for k < card
+void launch_nd_unique_emit(const uint64_t* words, int64_t n, const uint32_t* tile_off, int64_t vmin, int64_t* vals,
+                           int64_t card, hipStream_t s);
+// ids[r] = lower bound of v[r] in vals[0 .. card)
+void launch_nd_encode(const ColView& v, int64_t nrows, const int64_t* vals, uint32_t card, uint32_t* ids, hipStream_t s);
 // Row predicate of a filter on a numeric column: the reference evaluates it per row as a post-filter
 // (QueryableIndexStorageAdapter.makeCursors :244-260 -> FilteredOffset.java:40-105) through the
 // column's ValueMatcher ({Long,Float,Double}ValueMatcherColumnSelectorStrategy, the filters'

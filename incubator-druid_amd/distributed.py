@@ -339,6 +339,10 @@ class GroupByExchange:
         self.world, self.rank = dist.get_world_size(), dist.get_rank()
         self.engine = engine if engine is not None else NativeMerge(segments[0].context)
         nd = len(query.dimensions)
+        for d in query.dimensions:  # the cluster dictionaries below are unions of string dictionaries
+            if query.dimension_type(d) != "STRING" or any(
+                    hasattr(s, "column_type") and s.column_type(d) == R.N.COL_LONG for s in segments):
+                raise R.N.UnsupportedQuery(2, f"cross-process groupBy merge over the long dimension {d}")
         # this rank's merged dictionaries: the union of its segments' dictionaries (a segment without
         # the column contributes null), exactly as dg_groupby_run builds them
         local = []

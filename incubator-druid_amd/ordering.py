@@ -223,6 +223,31 @@ def sort_key(ordering: str, inverted: bool = False):
     return fn
 
 
+# ---- long dimensions (a groupBy dimension over a LONG column) ---------------------------------
+def long_text_key(v: int) -> str:
+    """String.valueOf(long) as a sort key: Java String.compareTo of the decimal text ('-' < digits, then
+    digit by digit, the shorter first: "-5" < "10" < "9"). The text is ASCII, so Python's str order is
+    compareTo's. The order of a long dimension whose output type is STRING
+    (GroupByQueryEngineV2.convertRowTypesToOutputTypes :689-698 turns the value into its text before
+    GroupByMergingQueryRunnerV2 merges)."""
+    return str(int(v))
+
+
+def long_dimension_key(output_type: str):
+    """Merge order of a long dimension's values by output type: LONG = Longs.compare
+    (LongRowBasedKeySerdeHelper, RowBasedGrouperHelper.java:1389-1437), STRING = long_text_key."""
+    return int if output_type == "LONG" else long_text_key
+
+
+def long_order_key(ordering: str):
+    """GroupByQuery.compareDimsForLimitPushDown (:600-633) over a numeric-typed dimension: the NUMERIC
+    comparator compares the longs, any other comparator compares String.valueOf of them."""
+    if ordering == "numeric":
+        return int
+    key = sort_key(ordering)
+    return lambda v: key(str(int(v)))
+
+
 class DictionaryOrder:
     """Rank of every id of one sorted dictionary under a topN comparator (dense: comparator-equal
     values share a rank), plus the previousStop cut (`min_rank`)."""

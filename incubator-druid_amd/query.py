@@ -901,11 +901,21 @@ class HavingSpec:
         return {"type": self.type}
 
 
+# ValueType names a DimensionSpec's outputType may carry (segment/column/ValueType.java); the engine groups
+# with STRING and LONG and refuses the others
+DIMENSION_OUTPUT_TYPES = ("STRING", "LONG", "FLOAT", "DOUBLE")
+
+
 @dataclass
 class GroupByQuery(BaseQuery):
+    """dimensions: the grouping columns' names; a dimension may be given as a DefaultDimensionSpec
+    ({"type": "default", "dimension": ..., "outputType": "STRING" | "LONG"},
+    query/dimension/DefaultDimensionSpec.java:68-78, outputType defaults to STRING). dimensionTypes: the
+    output type of every dimension, parallel to `dimensions`."""
     dimensions: List[str] = field(default_factory=list)
     limitSpec: Optional[DefaultLimitSpec] = None
     having: Optional[HavingSpec] = None
+    dimensionTypes: Optional[List[str]] = None
 
     def __post_init__(self):
         super().__post_init__()
@@ -913,15 +923,34 @@ class GroupByQuery(BaseQuery):
             self.limitSpec = DefaultLimitSpec.from_json(self.limitSpec)
         if isinstance(self.having, dict):
             self.having = HavingSpec.from_json(self.having)
-        dims = []
-        for d in self.dimensions:
+        given = list(self.dimensionTypes) if self.dimensionTypes is not None else None
+        if given is not None and len(given) != len(self.dimensions):
+            raise ValueError("dimensionTypes must name one output type per dimension")
+        dims, types = [], []
+        for i, d in enumerate(self.dimensions):
+            t = given[i] if given is not None else "STRING"
             if isinstance(d, dict):
+                if d.get("type", "default") != "default":
+                    raise ValueError(f"unsupported dimension spec {d.get('type')!r}")
                 if d.get("extractionFn") is not None:
                     raise ValueError("extraction functions are out of scope")
+                if d.get("outputName") not in (None, d["dimension"]):
+                    raise ValueError("renamed dimensions (outputName) are out of scope")
+                if d.get("outputType") is not None:
+                    t = d["outputType"]
                 dims.append(d["dimension"])
             else:
                 dims.append(d)
+            t = str(t).upper()
+            if t not in DIMENSION_OUTPUT_TYPES:
+                raise ValueError(f"unknown outputType {t!r}")
+            types.append(t)
         self.dimensions = dims
+        self.dimensionTypes = types
+
+    def dimension_type(self, name: str) -> str:
+        """The output type of the grouping dimension `name` (STRING for anything else)."""
+        return self.dimensionTypes[self.dimensions.index(name)] if name in self.dimensions else "STRING"
 
     def _ctx_bool(self, key: str, default: bool) -> bool:
         v = (self.context or {}).get(key, default)
@@ -975,7 +1004,11 @@ class GroupByQuery(BaseQuery):
 
     def to_json(self):
         js = self._base_json("groupBy")
-        js["dimensions"] = list(self.dimensions)
+        if all(t == "STRING" for t in self.dimensionTypes):
+            js["dimensions"] = list(self.dimensions)
+        else:  # DefaultDimensionSpec JSON: the output types travel with the dimensions
+            js["dimensions"] = [{"type": "default", "dimension": d, "outputName": d, "outputType": t}
+                                for d, t in zip(self.dimensions, self.dimensionTypes)]
         if self.limitSpec is not None:
             js["limitSpec"] = self.limitSpec.to_json()
         if self.having is not None:
@@ -1174,7 +1207,7 @@ def query_from_json(js: Dict[str, Any]):
         return TopNQuery(dimension=js["dimension"], metric=js["metric"], threshold=int(js["threshold"]), **common)
     if qt == "groupBy":
         return GroupByQuery(dimensions=js.get("dimensions", []), limitSpec=js.get("limitSpec"),
-                            having=js.get("having"), **common)
+                            having=js.get("having"), dimensionTypes=js.get("dimensionTypes"), **common)
     if qt == "search":
         return SearchQuery(searchDimensions=js.get("searchDimensions") or [], query=js.get("query"),
                            sort=js.get("sort") or "lexicographic", limit=int(js.get("limit", 0) or 0), **common)

@@ -748,11 +748,27 @@ class GroupByResult:
         self._dicts = dictionaries
         self.time_map: Optional[np.ndarray] = None  # bucket index -> time (a dg_merge over a calendar grid)
 
-    def dictionary(self, d: int) -> List[Optional[str]]:
+    def dim_types(self, d: int) -> Tuple[int, int]:
+        """(column type, output type) of dimension d as N.COL_* (dg_result_dim_type); a dg_merge result has
+        the caller's dictionaries: strings."""
+        if self._dicts is not None:
+            return N.COL_STRING, N.COL_STRING
+        ct, ot = ctypes.c_int32(), ctypes.c_int32()
+        N.check(N.lib().dg_result_dim_type(self.handle, d, ctypes.byref(ct), ctypes.byref(ot)))
+        return ct.value, ot.value
+
+    def dictionary(self, d: int) -> List:
+        """The merged dictionary of dimension d in merged-id order: strings (None = null); Python ints for
+        a long dimension whose output type is LONG (dg_result_dim_longs), its values' decimal strings when
+        the output type is STRING."""
         if self._dicts is not None:
             return self._dicts[d]
         L = N.lib()
         card = int(L.dg_result_dim_cardinality(self.handle, d))
+        if self.dim_types(d) == (N.COL_LONG, N.COL_LONG):
+            vals = np.zeros(max(card, 1), dtype=np.int64)
+            N.check(L.dg_result_dim_longs(self.handle, d, vals.ctypes.data))
+            return vals[:card].tolist()
         offs = np.zeros(card + 1, dtype=np.int64)
         total = ctypes.c_int64()
         N.check(L.dg_result_dim_dictionary(self.handle, d, None, None, ctypes.byref(total)))
@@ -821,7 +837,15 @@ class GroupByResult:
                 continue
             seen.add(d)
             rank = None
-            if ordering != "lexicographic" or _beyond_bmp_low(self.dictionary(d)):
+            if q.dimensionTypes[d] == "LONG":
+                # compareDimsForLimitPushDown (GroupByQuery.java:600-633) over a numeric-typed dimension: NUMERIC
+                # compares the longs (the id order of a LONG-output dimension), any other comparator
+                # compares String.valueOf of them
+                if ordering != "numeric":
+                    texts = [str(v) for v in self.dictionary(d)]
+                    rank = np.ascontiguousarray(O.DictionaryOrder(texts, ordering).rank, dtype=np.int32)
+                    keep.append(rank)
+            elif ordering != "lexicographic" or _beyond_bmp_low(self.dictionary(d)):
                 rank = np.ascontiguousarray(O.DictionaryOrder(self.dictionary(d), ordering).rank, dtype=np.int32)
                 keep.append(rank)
             cols.append(N.dg_order_column(d, int(desc), rank.ctypes.data if rank is not None else None))
@@ -884,7 +908,17 @@ def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     m = N.dg_metrics()
     t0 = time.perf_counter()
     opts = grouper_options(query)
-    if opts is None:
+    if any(t != "STRING" for t in query.dimensionTypes):
+        # DimensionSpec.getOutputType of every dimension goes with it (dg_groupby_run_dims)
+        types = {"STRING": N.COL_STRING, "LONG": N.COL_LONG, "FLOAT": N.COL_FLOAT, "DOUBLE": N.COL_DOUBLE}
+        specs = (N.dg_dimension * max(nd, 1))()
+        for i, t in enumerate(query.dimensionTypes):
+            specs[i].dimension = dims[i]
+            specs[i].output_type = types[t]
+        o = N.dg_groupby_opts(opts[0], 0, opts[1]) if opts is not None else None
+        N.check(N.lib().dg_groupby_run_dims(_handles(segments), len(segments), ctypes.byref(scan), specs, nd,
+                                            ctypes.byref(o) if o is not None else None, ctypes.byref(res), ctypes.byref(m)))
+    elif opts is None:
         N.check(N.lib().dg_groupby_run(_handles(segments), len(segments), ctypes.byref(scan), ctypes.byref(g),
                                        ctypes.byref(res), ctypes.byref(m)))
     else:
@@ -996,6 +1030,9 @@ def merge_groupby_columnar(query: Q.GroupByQuery, partials: Sequence[GroupByPart
     dim_values = []
     coded = all(p.codes is not None for p in parts)
     for d in range(nd):
+        # a LONG-output dimension's values are longs and merge in numeric order (LongRowBasedKeySerdeHelper,
+        # RowBasedGrouperHelper.java:1389-1437); every other dimension's are strings in Java String order
+        vkey = int if query.dimensionTypes[d] == "LONG" else _java_key
         if coded:
             # segment dictionaries are sorted (GenericIndexed STRING_STRATEGY): merge them into one
             # global dictionary and remap each segment's ids with one vectorised lookup
@@ -1003,7 +1040,7 @@ def merge_groupby_columnar(query: Q.GroupByQuery, partials: Sequence[GroupByPart
             if all(dd is dicts[0] or dd == dicts[0] for dd in dicts[1:]):
                 uniq, maps = list(dicts[0]), [None] * len(parts)
             else:
-                uniq = sorted(set().union(*map(set, dicts)), key=_java_key)
+                uniq = sorted(set().union(*map(set, dicts)), key=vkey)
                 index = {v: i for i, v in enumerate(uniq)}
                 maps = [np.array([index[v] for v in dd], dtype=np.int64) for dd in dicts]
             dim_codes.append(np.concatenate([p.codes[d].astype(np.int64) if m is None else m[p.codes[d]]
@@ -1011,7 +1048,7 @@ def merge_groupby_columnar(query: Q.GroupByQuery, partials: Sequence[GroupByPart
             dim_values.append(np.array(uniq, dtype=object))
             continue
         col = np.concatenate([p.dims[d] for p in parts])
-        uniq = sorted(set(col.tolist()), key=_java_key)  # global dictionary in Java order, null first
+        uniq = sorted(set(col.tolist()), key=vkey)  # global dictionary in Java order, null first
         index = {v: i for i, v in enumerate(uniq)}
         dim_codes.append(np.fromiter((index[v] for v in col), dtype=np.int64, count=len(col)))
         dim_values.append(np.array(uniq, dtype=object))
@@ -1102,7 +1139,8 @@ def merge_groupby(query: Q.GroupByQuery, partials: Sequence[GroupByPartial]) -> 
         rows = sorted(rows, key=_push_down_key(query))[:query.limitSpec.limit]
     elif query._ctx_bool("sortByDimsFirst", False) and not query.granularity.is_all:
         # getRowOrdering(false) with sortByDimsFirst: dimensions, then time (GroupByQuery.java:543-553)
-        rows.sort(key=lambda r: tuple(_java_key(r.event[d]) for d in query.dimensions))
+        keys = [int if t == "LONG" else _java_key for t in query.dimensionTypes]
+        rows.sort(key=lambda r: tuple(k(r.event[d]) for k, d in zip(keys, query.dimensions)))
     return postprocess_groupby(query, rows)
 
 
@@ -1110,11 +1148,14 @@ def _push_down_key(query: Q.GroupByQuery):
     """Sort key of GroupByQuery.getRowOrderingForPushDown (:423-528): ORDER BY dimensions under their
     comparator and direction, the other dimensions ascending under LEXICOGRAPHIC, the time first (last
     with sortByDimsFirst; absent for ALL)."""
+    def dim_key(name, ordering):  # (a LONG-output dimension: compareDimsForLimitPushDown :600-633)
+        return O.long_order_key(ordering) if query.dimension_type(name) == "LONG" else O.sort_key(ordering)
+
     fields, seen = [], set()
     for c in query.limitSpec.columns:
-        fields.append((c.dimension, O.sort_key(c.dimensionOrder), c.direction == "descending"))
+        fields.append((c.dimension, dim_key(c.dimension, c.dimensionOrder), c.direction == "descending"))
         seen.add(c.dimension)
-    fields += [(d, O.sort_key("lexicographic"), False) for d in query.dimensions if d not in seen]
+    fields += [(d, dim_key(d, "lexicographic"), False) for d in query.dimensions if d not in seen]
     gran_all = query.granularity.is_all
     dims_first = query._ctx_bool("sortByDimsFirst", False)
 
@@ -1190,19 +1231,32 @@ def _limit_needs_sort(query: Q.GroupByQuery) -> bool:
             return True
         if c.dimension not in query.dimensions:
             raise ValueError(f"Unknown column in order clause[{c.dimension}]")
-        # string dimensions: the natural comparator is LEXICOGRAPHIC
-        if c.direction != "ascending" or c.dimensionOrder != "lexicographic" or c.dimension != query.dimensions[i]:
+        # string dimensions: the natural comparator is LEXICOGRAPHIC; numeric-typed ones: NUMERIC
+        natural = "numeric" if query.dimension_type(c.dimension) == "LONG" else "lexicographic"
+        if c.direction != "ascending" or c.dimensionOrder != natural or c.dimension != query.dimensions[i]:
             return True
     return not query.granularity.is_all and query._ctx_bool("sortByDimsFirst", False)
 
 
+def _having_dimensions(h: Q.HavingSpec) -> List[str]:
+    return ([h.dimension] if h.type == "dimSelector" else []) + [d for x in h.specs for d in _having_dimensions(x)]
+
+
 def postprocess_groupby(query: Q.GroupByQuery, rows: List[Q.Row]) -> List[Q.Row]:
+    """A having spec that selects on a LONG-output dimension, or a limit spec that has to sort on one, is
+    refused (UnsupportedQuery): the host rules here are the string dimensions'."""
     if query.having is not None:
+        for d in _having_dimensions(query.having):
+            if query.dimension_type(d) == "LONG":
+                raise N.UnsupportedQuery(2, f"having spec on the LONG-output dimension {d}")
         rows = [r for r in rows if _having_eval(query.having, r)]
     ls = query.limitSpec
     if ls is None:
         return rows
     if _limit_needs_sort(query):
+        for c in ls.columns:
+            if query.dimension_type(c.dimension) == "LONG":
+                raise N.UnsupportedQuery(2, f"limit spec sorts on the LONG-output dimension {c.dimension}")
         aggs = {a.name: a for a in query.aggregations}
         dims = set(query.dimensions)
         parts = []

@@ -103,6 +103,14 @@ class GpuSegment:
     def device_bytes(self) -> int:
         return int(N.lib().dg_segment_device_bytes(self.handle))
 
+    def long_dim_info(self, column: str) -> Dict:
+        """The cached long-dimension encoding of a LONG column (dg_debug_long_dim_info): whether a groupBy
+        has built it, its cardinality, the HBM it holds and the device time of its build."""
+        built, card, nbytes, ms = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        N.check(N.lib().dg_debug_long_dim_info(self.handle, column.encode(), ctypes.byref(built), ctypes.byref(card),
+                                               ctypes.byref(nbytes), ctypes.byref(ms)))
+        return {"built": bool(built.value), "cardinality": card.value, "device_bytes": nbytes.value, "build_ms": ms.value}
+
     def cardinality(self, dim: str) -> int:
         return int(N.lib().dg_segment_dim_cardinality(self.handle, dim.encode()))
 
