@@ -19,6 +19,9 @@
  *                               TimeseriesQueryEngine.java:40-111)
  *   dg_topn_run              <- TopNQueryRunnerFactory.createRunner(segment).run (query/topn/TopNQueryRunnerFactory.java:61-90,
  *                               TopNQueryEngine.java:60-160 -> PooledTopNAlgorithm + TopNNumericResultBuilder)
+ *   dg_topn_run_opts         <- the same over a LONG / FLOAT / DOUBLE column: TopNQueryEngine.getMapFn (:141-148) ->
+ *                               DimExtractionTopNAlgorithm + NumericTopNColumnSelectorStrategy
+ *                               (query/topn/types/NumericTopNColumnSelectorStrategy.java:81-171)
  *   dg_segment_set_dim_order <- StringComparator.compare over one dictionary (query/ordering/StringComparators.java),
  *                               the order DimensionTopNMetricSpec / TopNLexicographicResultBuilder ranks values by
  *   dg_topn_merge            <- TopNBinaryFn.apply fold of QueryRunnerFactory.mergeRunners (query/topn/TopNBinaryFn.java:75-135)
@@ -367,6 +370,60 @@ typedef struct {
 int dg_topn_run(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_topn* topn,
                 int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics);
 
+/* topN over a numeric dimension. TopNQueryEngine.getMapFn (query/topn/TopNQueryEngine.java:141-148) sends a
+ * LONG, FLOAT or DOUBLE column to DimExtractionTopNAlgorithm with a NumericTopNColumnSelectorStrategy
+ * (types/TopNColumnSelectorStrategyFactory.java:43-69), which aggregates the rows into a map keyed by the long
+ * itself, Float.floatToIntBits(v) or Double.doubleToLongBits(v) (types/NumericTopNColumnSelectorStrategy.java:
+ * 81-151): every NaN is one value, -0.0 and 0.0 are two. The engine dictionary-encodes the column on the device
+ * at its first use (the encoding dg_groupby_run_dims builds for a LONG dimension, shared with it; see
+ * dg_segment_numeric_dim_info) and runs the topN over the ids: result ids index the column's distinct values in
+ * ascending Long / Float / Double.compareTo order, and dg_segment_numeric_dim_values gives their values.
+ *
+ *   output_type  DimensionSpec.getOutputType. Supported: a LONG column with DG_COL_LONG or DG_COL_STRING (the
+ *                entries carry String.valueOf(value)), a FLOAT column with DG_COL_FLOAT, a DOUBLE column with
+ *                DG_COL_DOUBLE. Metric ties are broken by the output value's compareTo (TopNNumericResultBuilder.
+ *                java:94-107,185-191,219-236): numerically, or for DG_COL_STRING by String.compareTo of the decimal
+ *                text. A dimension-ordered spec (topn->dim_order; TopNLexicographicResultBuilder.java:66-125
+ *                compares Objects.toString(value)) is supported on a LONG column for DG_ORDER_NUMERIC and
+ *                DG_ORDER_LEXICOGRAPHIC, plain and inverted; the engine derives the ranks itself
+ *                (dg_segment_set_dim_order refuses a numeric column).
+ *   out_cut_ties The reference offers the map's entries to the builder in its hash map's iteration order
+ *                (updateDimExtractionResults, NumericTopNColumnSelectorStrategy.java:154-171), and the builder
+ *                refuses an entry whose metric equals the full queue's minimum: every value above the K-th largest
+ *                metric is in its result and none below, but WHICH of the values tied with the K-th it keeps is
+ *                arbitrary. The engine offers the values in ascending order of the output type's comparator (as a
+ *                string dimension's ids are) and reports here, per list, how many values whose metric equals the
+ *                last entry's are not in the list. 0: the list is what the reference returns under any order.
+ *
+ * DG_ERR_UNSUPPORTED before any launch, naming the column: any other (column, output) pair (the reference
+ * aggregates by the OUTPUT type's key there, which is many-to-one), a column that is numeric in some of the
+ * call's segments with a cursor and a string or missing in others, previous_stop on a numeric dimension,
+ * DG_ORDER_ALPHANUMERIC / DG_ORDER_STRLEN on a numeric dimension, any dimension ordering on FLOAT / DOUBLE (it
+ * would need Float.toString), a numeric output type on a string column. A string dimension with
+ * DG_COL_STRING is dg_topn_run. */
+typedef struct {
+  int32_t output_type;    /* DG_COL_STRING | DG_COL_LONG | DG_COL_FLOAT | DG_COL_DOUBLE; 0 = DG_COL_STRING */
+  int32_t reserved;
+  int32_t* out_cut_ties;  /* optional [n_segs * bucket_cap]: per list, values whose metric equals the last
+                             entry's and that are not in the list; 0 for a short list, a dimension-ordered
+                             spec and a string dimension */
+} dg_topn_opts;
+/* dg_topn_run with options (opts == NULL: dg_topn_run itself). */
+int dg_topn_run_opts(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_topn* topn,
+                     const dg_topn_opts* opts, int32_t* out_n, int32_t* out_ids, uint64_t* out_values,
+                     dg_metrics* metrics);
+/* Values of result ids of a numeric dimension: out[k] = the value of ids[k] as an 8-byte slot in the aggregate
+ * slot encoding (LONG: int64; DOUBLE: the double; FLOAT: the float32 in the first 4 bytes), what
+ * convertAggregatorStoreKeyToColumnValue gives for the map key; a NaN is the canonical one. DG_ERR_ARG: not a
+ * numeric column, no encoding built yet, or an id outside it. */
+int dg_segment_numeric_dim_values(dg_segment* seg, const char* column, const int32_t* ids, int32_t n, uint64_t* out);
+/* The cached encoding of a numeric column (dg_debug_long_dim_info for LONG, FLOAT and DOUBLE columns; that call
+ * keeps its LONG-only contract): *built, *cardinality, *device_bytes (ids 4 B per row + 8 B per value, part of
+ * dg_segment_device_bytes), *build_ms. Any output may be NULL. DG_ERR_NOT_FOUND: no such column; DG_ERR_ARG: not
+ * a numeric column. */
+int dg_segment_numeric_dim_info(dg_segment* seg, const char* column, int32_t* built, int64_t* cardinality,
+                                int64_t* device_bytes, double* build_ms);
+
 /* TopNBinaryFn fold (query/topn/TopNBinaryFn.java:75-135) of per-segment topN lists, as
  * TopNQueryQueryToolChest.mergeResults applies it over the per-segment runners' results
  * (QueryRunnerFactory.mergeRunners): lists in merge order (result timestamp, then segment index),
@@ -387,6 +444,15 @@ typedef struct {
 
 int dg_topn_merge(dg_segment* const* segs, const dg_scan* scan, const dg_topn* topn, const dg_topn_lists* in,
                   int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values);
+/* dg_topn_merge with options (opts == NULL: dg_topn_merge itself; out_cut_ties is not used). Segment mode over a
+ * numeric dimension (the pairs of dg_topn_run_opts, the same refusals): TopNBinaryFn keys its map by the value
+ * object, so keys (ids into each segment's value list) are one value when the values' map keys are equal, and
+ * the builder breaks metric ties by the output type's compareTo (DG_COL_STRING on a LONG column: String.compareTo
+ * of the decimal text). Global mode: the keys are the caller's and compare as signed 64-bit integers, whatever
+ * the output type (a LONG dimension's values themselves). */
+int dg_topn_merge_opts(dg_segment* const* segs, const dg_scan* scan, const dg_topn* topn, const dg_topn_lists* in,
+                       const dg_topn_opts* opts, int32_t* out_n, int32_t* out_list, int64_t* out_keys,
+                       uint64_t* out_values);
 
 /* ---- search ----
  * Per-value hit counts of a search query (query/search/SearchQueryRunner.java:207-260). The caller
@@ -762,7 +828,7 @@ int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t iters, doubl
 int dg_debug_groupby_totals_source(dg_context* ctx, int32_t* source);
 
 /* The cached long-dimension encoding of a LONG column (built by the first dg_groupby_run* that groups by
- * it; no reference counterpart, the reference reads the long per row): *built = 0 / 1, *cardinality = its
+ * it or the first dg_topn_run_opts over it; no reference counterpart, the reference reads the long per row): *built = 0 / 1, *cardinality = its
  * distinct values, *device_bytes = HBM held by the ids (4 B per row) and the value list (8 B per value),
  * part of dg_segment_device_bytes, *build_ms = device time of the build. Any output may be NULL.
  * DG_ERR_NOT_FOUND: no such column; DG_ERR_ARG: not a LONG column. */

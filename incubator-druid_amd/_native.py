@@ -108,6 +108,10 @@ class dg_topn_lists(ctypes.Structure):
                 ("keys", ctypes.c_void_p), ("values", ctypes.c_void_p)]
 
 
+class dg_topn_opts(ctypes.Structure):
+    _fields_ = [("output_type", ctypes.c_int32), ("reserved", ctypes.c_int32), ("out_cut_ties", ctypes.c_void_p)]
+
+
 class dg_groupby(ctypes.Structure):
     _fields_ = [("dimensions", ctypes.POINTER(ctypes.c_char_p)), ("n_dims", ctypes.c_int32)]
 
@@ -183,6 +187,7 @@ EXPORTS = [
     "dg_rows_run", "dg_rowset_rows", "dg_rowset_column_info", "dg_rowset_fetch", "dg_rowset_release",
     "dg_segment_num_dimensions", "dg_segment_dimension_name", "dg_debug_groupby_totals_source",
     "dg_groupby_run_dims", "dg_result_dim_type", "dg_result_dim_longs", "dg_debug_long_dim_info",
+    "dg_topn_run_opts", "dg_topn_merge_opts", "dg_segment_numeric_dim_values", "dg_segment_numeric_dim_info",
 ]
 
 _lib = None
@@ -271,6 +276,12 @@ def lib():
         "dg_result_dim_type": (ctypes.c_int, [vp, i32, P(i32), P(i32)]),
         "dg_result_dim_longs": (ctypes.c_int, [vp, i32, vp]),
         "dg_debug_long_dim_info": (ctypes.c_int, [vp, cp, P(i32), P(i64), P(i64), P(ctypes.c_double)]),
+        "dg_topn_run_opts": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_topn), P(dg_topn_opts), vp, vp, vp,
+                                            P(dg_metrics)]),
+        "dg_topn_merge_opts": (ctypes.c_int, [vp, P(dg_scan), P(dg_topn), P(dg_topn_lists), P(dg_topn_opts), P(i32),
+                                              vp, vp, vp]),
+        "dg_segment_numeric_dim_values": (ctypes.c_int, [vp, cp, vp, i32, vp]),
+        "dg_segment_numeric_dim_info": (ctypes.c_int, [vp, cp, P(i32), P(i64), P(i64), P(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)

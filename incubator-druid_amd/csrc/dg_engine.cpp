@@ -614,6 +614,7 @@ static void decode_metrics(const DecodeBatch& db, const DecodeBatch& side, dg_me
 }
 static int column_view(const Column* c, CallScratch* cs, DecodeBatch* db, ColView* v, hipStream_t st);
 static int multi_view(const Column* c, CallScratch* cs, DecodeBatch* db, ColView* vals, ColView* offs, hipStream_t st);
+static int build_num_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c, hipStream_t st);
 static int run_decodes(CallScratch* cs, DecodeBatch* db, hipStream_t st, uint64_t* d_prof = nullptr, bool overlap = false);
 static int run_decodes_only(CallScratch* cs, DecodeBatch* db, hipStream_t st, uint64_t* d_prof, bool overlap = false);
 
@@ -2857,8 +2858,53 @@ static uint64_t metric_key_host(uint64_t slot, int kind, int inverted) {
   return inverted ? ~k : k;
 }
 
-int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, int32_t* out_n, int32_t* out_ids,
-                uint64_t* out_values, dg_metrics* metrics) {
+// The host-derived orders of a numeric dimension's ids, cached with the column. nd_text (a LONG column,
+// when `text` or a LEXICOGRAPHIC slot asks for it): the id's position in String.compareTo order of the
+// decimal text. The rank table of order slot `slot` (2 * DG_ORDER_* + inverted, -1 = none), what
+// dg_segment_set_dim_order hands in for a string column: TopNLexicographicResultBuilder.java:66-125
+// compares Objects.toString(value) under the spec's StringComparator, which for NUMERIC orders the decimal
+// texts as numbers (the id) and for LEXICOGRAPHIC as strings (nd_text); an inverted spec reverses it. No
+// two values compare equal under either.
+static int numeric_dim_orders(Column* c, bool text, int slot) {
+  const int32_t card = (int32_t)c->nd_card;
+  const bool lex = slot >= 0 && (slot >> 1) == DG_ORDER_LEXICOGRAPHIC;
+  if ((text || lex) && (int64_t)c->nd_text.size() != c->nd_card) {
+    std::vector<std::pair<LongTextKey, int32_t>> keyed((size_t)card);
+    for (int32_t id = 0; id < card; ++id) keyed[id] = {long_text_key(c->nd_host[id]), id};
+    std::sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    c->nd_text.resize((size_t)card);
+    for (int32_t k = 0; k < card; ++k) c->nd_text[keyed[k].second] = k;
+  }
+  if (slot < 0 || c->order_set[slot]) return DG_OK;
+  std::vector<int32_t> rank((size_t)card);
+  for (int32_t id = 0; id < card; ++id) {
+    const int32_t r = lex ? c->nd_text[id] : id;
+    rank[id] = (slot & 1) ? card - 1 - r : r;
+  }
+  DevBuf& b = c->order_rank[slot];
+  if (!b.alloc(sizeof(int32_t) * (size_t)std::max(card, 1))) return set_error(DG_ERR_OOM, "order of %s", c->name.c_str());
+  if (card) DG_HIP(hipMemcpy(b.p, rank.data(), sizeof(int32_t) * (size_t)card, hipMemcpyHostToDevice));
+  c->order_host[slot].swap(rank);
+  c->order_ties[slot] = 0;
+  c->order_set[slot] = true;
+  return DG_OK;
+}
+
+// dg_topn_run (opts = NULL) and dg_topn_run_opts.
+//
+// A numeric dimension (the column is LONG, FLOAT or DOUBLE in every segment of the call that has a cursor;
+// TopNQueryEngine.getMapFn, TopNQueryEngine.java:141-148, sends it to DimExtractionTopNAlgorithm with a
+// NumericTopNColumnSelectorStrategy, which keys the rows by the long itself / floatToIntBits /
+// doubleToLongBits, NumericTopNColumnSelectorStrategy.java:81-151): the column's cached encoding
+// (Column::nd_*, build_num_dim, built here at first use) is the key view and the value list's length the
+// cardinality; everything below runs as over a string column's ids. Result ids index the value list.
+// Id order is the order of Long / Float / Double.compareTo, which the result builder breaks metric ties
+// by (TopNNumericResultBuilder.java:94-107); a LONG column with output type STRING carries
+// String.valueOf(value) and its candidates are offered and tie-broken in String.compareTo order of the
+// decimal text (Column::nd_text). The reference offers the values in its hash map's iteration order, so
+// which values tied with the K-th metric it keeps is arbitrary: out_cut_ties reports how many were left out.
+static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, const dg_topn_opts* opts,
+                         int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics) {
   auto t0 = std::chrono::steady_clock::now();
   HostTrace ht;
   Context* ctx;
@@ -2881,11 +2927,77 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
   AggPlan plan;
   rc = make_plan(q, &plan);
   if (rc) return rc;
+  // what the dimension is over the segments with a cursor; everything unsupported is refused here,
+  // before any launch
+  const int32_t out_type = opts && opts->output_type ? opts->output_type : DG_COL_STRING;
+  if (out_type != DG_COL_STRING && !is_numeric_type(out_type))
+    return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: output type %d", t->dimension, out_type);
+  int num_type = 0;  // DG_COL_LONG / FLOAT / DOUBLE: a numeric dimension; 0: a string (or missing) one
+  std::vector<char> has_cursor(std::max(n, 1), 0);
+  {
+    int n_num = 0, n_other = 0;
+    for (int i = 0; i < n; ++i) {
+      const Segment* seg = reinterpret_cast<const Segment*>(segs[i]);
+      has_cursor[i] = plan_cursors(seg, i, q, gr).any;
+      if (!has_cursor[i]) continue;
+      const Column* c = seg->find(t->dimension);
+      if (c && is_numeric_type(c->type)) {
+        if (num_type && num_type != c->type)
+          return set_error(DG_ERR_UNSUPPORTED, "topN column %s has different numeric types in the call's segments", t->dimension);
+        num_type = c->type;
+        ++n_num;
+      } else {
+        ++n_other;
+      }
+    }
+    if (n_num && n_other)
+      return set_error(DG_ERR_UNSUPPORTED, "topN column %s is numeric in %d of the call's segments and a string or missing in %d",
+                       t->dimension, n_num, n_other);
+    if (!n_num && n_other && out_type != DG_COL_STRING)
+      return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: numeric output type on a string column", t->dimension);
+  }
+  if (num_type) {
+    // the reference aggregates by the OUTPUT type's key (many-to-one for any other pair)
+    const bool pair = out_type == num_type || (num_type == DG_COL_LONG && out_type == DG_COL_STRING);
+    if (!pair)
+      return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: output type %d on a column of type %d", t->dimension, out_type, num_type);
+    if (t->previous_stop) return set_error(DG_ERR_UNSUPPORTED, "topN previousStop on numeric dimension %s", t->dimension);
+    if (dim) {
+      const int ord = t->dim_order >> 1;
+      if (num_type != DG_COL_LONG)
+        return set_error(DG_ERR_UNSUPPORTED, "topN dimension ordering on %s column %s", num_type == DG_COL_FLOAT ? "FLOAT" : "DOUBLE",
+                         t->dimension);
+      if (ord != DG_ORDER_LEXICOGRAPHIC && ord != DG_ORDER_NUMERIC)
+        return set_error(DG_ERR_UNSUPPORTED, "topN %s ordering on numeric dimension %s", ord == DG_ORDER_STRLEN ? "STRLEN" : "ALPHANUMERIC",
+                         t->dimension);
+    }
+  }
+  const bool text_order = num_type == DG_COL_LONG && !dim && out_type == DG_COL_STRING;
+  if (opts && opts->out_cut_ties)
+    for (int64_t L = 0; L < (int64_t)n * bcap; ++L) opts->out_cut_ties[L] = 0;
   CallGuard g(ctx);
   CallScratch* cs = g.cs;
   Interrupt intr(q, t0);
   cs->intr = &intr;
   hipStream_t st = ctx->stream;
+  if (num_type) {
+    // the encodings this call is the first to need (each build ends with a wait, after which its scratch
+    // is the call's again), the decimal-text positions and the dimension order's ranks, all cached with
+    // the column
+    for (int i = 0; i < n; ++i) {
+      if (!has_cursor[i]) continue;
+      Segment* seg = reinterpret_cast<Segment*>(segs[i]);
+      Column* c = seg->find(t->dimension);
+      if (!c->nd_ready) {
+        rc = build_num_dim(ctx, cs, seg, c, st);
+        if (rc) return rc;
+        cs->reset();
+        cs->intr = &intr;
+      }
+      rc = numeric_dim_orders(c, text_order, dim ? t->dim_order : -1);
+      if (rc) return rc;
+    }
+  }
   rc = upload_grain(cs, &gr, st);
   if (rc) return rc;
   dg_metrics m;
@@ -2899,7 +3011,7 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
                 !env_on("DG_NO_TOPN_INDEX");
   for (int i = 0; i < n && use_ix; ++i) {
     const Column* c = reinterpret_cast<Segment*>(segs[i])->find(t->dimension);
-    use_ix = c && c->type == DG_COL_STRING && !c->multi_value;
+    use_ix = c && (c->type == DG_COL_STRING || is_numeric_type(c->type)) && !c->multi_value;
   }
   std::vector<char> ix_skip(n, 0);  // segment i's ids are not decoded (its index is built)
   std::vector<Cursors> cur(n);
@@ -2921,7 +3033,8 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
     ScanJob& j = jobs[i];
     memset(&j, 0, sizeof j);
     Column* dc = seg->find(t->dimension);
-    if (dc && dc->type != DG_COL_STRING) return set_error(DG_ERR_UNSUPPORTED, "topN on non-string dimension %s", t->dimension);
+    if (dc && dc->type != DG_COL_STRING && !num_type)
+      return set_error(DG_ERR_UNSUPPORTED, "topN on column %s of an unsupported type", t->dimension);
     uint32_t* bits = nullptr;
     rc = build_bitset(seg, cs, q->filter, q->n_filter, &bits, &counts[i], st);
     if (rc) return rc;
@@ -2942,11 +3055,21 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
         any_multi = true;
       } else if (use_ix && dc->tix_ready) {
         ix_skip[i] = 1;
+      } else if (num_type) {
+        // the column's cached ids as one block of little-endian 4-byte ids (Column::nd_ids), read by
+        // load_id / load_ids4 like any id column (64-bit row offsets; the ids buffer is padded past a quad)
+        if (!dc->nd_ready || !dc->nd_ptr.p) return set_error(DG_ERR_ARG, "numeric dimension %s has no encoding", t->dimension);
+        j.key.blocks = dc->nd_ptr.as<const uint8_t*>();
+        j.key.log2_per = kNdLog2Per;
+        j.key.width = 4;
+        j.key.pad = 0;
+        j.key.kind = VIEW_IDS;
+        db.bytes += 4 * seg->nrows;
       } else {
         rc = column_view(dc, cs, &db, &j.key, st);
       }
       if (rc) return rc;
-      card[i] = std::max<int64_t>((int64_t)dc->dict.size(), 1);
+      card[i] = std::max<int64_t>(num_type ? dc->nd_card : (int64_t)dc->dict.size(), 1);
     } else {
       // missing dimension: every row has the null value -> one group (id 0)
       static_assert(sizeof(ColView) == 24, "ColView layout");
@@ -3081,7 +3204,8 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
         any_ties |= dim_ties[i] != 0;
       }
       int32_t lo = 0, hi = cd;
-      if (t->dim_order == 2 * DG_ORDER_LEXICOGRAPHIC) {
+      // (a numeric dimension has no dictionary range to cut: its ids are not in the comparator's order)
+      if (t->dim_order == 2 * DG_ORDER_LEXICOGRAPHIC && !num_type) {
         if (t->previous_stop) {
           // lookupId(previousStop) + 1, negated when missing; a missing dimension's selector
           // resolves only null / "" (to id 0)
@@ -3324,8 +3448,11 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
       uint64_t key;
       int32_t id;
       int32_t idx;
+      int32_t ord;  // position under the output type's comparator: the id, or its decimal text's position
     };
     const int K = t->threshold;
+    int32_t* cut_ties = num_type && !dim && opts && opts->out_cut_ties ? &opts->out_cut_ties[out_base[k]] : nullptr;
+    const int32_t* trank = text_order ? reinterpret_cast<Segment*>(segs[i])->find(t->dimension)->nd_text.data() : nullptr;
     if (dim) {
       // TopNLexicographicResultBuilder (TopNLexicographicResultBuilder.java:40-176) over the eligible
       // ids in id order: every non-null value is offered (shouldAdd compares the head's unset metric
@@ -3398,7 +3525,7 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
       continue;
     }
     std::vector<E> v;
-    if (ordered(k)) {
+    if (ordered(k) && !trank) {
       // k_topn_order sorted the candidates by (key desc, id asc) and left their records in that
       // order; keep every key > kth and, of the kth ties, those the builder's queue keeps (see
       // below), already in output order
@@ -3428,13 +3555,18 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
           emit(e);
         }
         out_n[out_base[k]] = (int32_t)nout;
+        if (cut_ties) *cut_ties = nc - nout;  // (every candidate not kept ties with the K-th key)
         continue;
       }
     }
     if ((rc = unpack(k))) return rc;
     std::vector<E> all(nc);
-    for (int c = 0; c < nc; ++c)
-      all[c] = E{metric_key_host(h_tab[k][(size_t)c * rec + 1 + t->metric_agg], mk, t->inverted), h_cand[k][c], c};
+    for (int c = 0; c < nc; ++c) {
+      const int32_t id = h_cand[k][c];
+      all[c] = E{metric_key_host(h_tab[k][(size_t)c * rec + 1 + t->metric_agg], mk, t->inverted), id, c, trank ? trank[id] : id};
+    }
+    // (String output of a LONG column: offered in the decimal text's order; the candidates are few)
+    if (trank) std::sort(all.begin(), all.end(), [](const E& a, const E& b) { return a.ord < b.ord; });
     // The candidates are the ids whose key >= the K-th largest key (kth), in id order. The builder's
     // priority queue (min-heap on (key, id), push when not full or top.key < key, pop the minimum
     // when over K) then keeps every key > kth and, of the kth ties, those pushed while it was not
@@ -3465,7 +3597,7 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
       }
       for (size_t q = popped; q < ties.size(); ++q) v.push_back(all[ties[q]]);
     } else {  // not reached for an exact K-th key; the builder's queue, literally
-      auto less = [](const E& a, const E& b) { return a.key != b.key ? a.key < b.key : a.id < b.id; };
+      auto less = [](const E& a, const E& b) { return a.key != b.key ? a.key < b.key : a.ord < b.ord; };
       auto gt = [&](const E& a, const E& b) { return less(b, a); };
       std::priority_queue<E, std::vector<E>, decltype(gt)> pq(gt);  // min-heap on (key, id)
       for (int c = 0; c < nc; ++c) {
@@ -3477,8 +3609,15 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
         pq.pop();
       }
     }
-    std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.key != b.key ? a.key > b.key : a.id < b.id; });
+    std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.key != b.key ? a.key > b.key : a.ord < b.ord; });
     out_n[out_base[k]] = (int32_t)v.size();
+    if (cut_ties && !v.empty() && (int)v.size() >= K) {  // values tied with the last kept metric and left out
+      const uint64_t last = v.back().key;
+      int32_t tied = 0, kept = 0;
+      for (const E& e : all) tied += e.key == last;
+      for (const E& e : v) kept += e.key == last;
+      *cut_ties = tied - kept;
+    }
     for (size_t e = 0; e < v.size(); ++e) {
       const int64_t o = out_base[k] * t->threshold + (int64_t)e;
       out_ids[o] = v[e].id;
@@ -3499,6 +3638,16 @@ int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_t
   ht.mark("done");
   if (metrics) *metrics = m;
   return DG_OK;
+}
+
+int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, int32_t* out_n, int32_t* out_ids,
+                uint64_t* out_values, dg_metrics* metrics) {
+  return topn_run_impl(segs, n, q, t, nullptr, out_n, out_ids, out_values, metrics);
+}
+
+int dg_topn_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, const dg_topn_opts* opts,
+                     int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics) {
+  return topn_run_impl(segs, n, q, t, opts, out_n, out_ids, out_values, metrics);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3860,10 +4009,18 @@ static uint64_t abi_metric_key(int kind, uint64_t v, int inverted) {
 
 extern "C" {
 
-int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in, int32_t* out_n,
-                  int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
+// dg_topn_merge (opts = NULL) and dg_topn_merge_opts. A numeric dimension in segment mode (the column is
+// LONG, FLOAT or DOUBLE in every list's segment): TopNBinaryFn keys its map by the value object, so two
+// entries are one value when their keys in the columns' value lists (Column::nd_host) are equal, and the
+// builder breaks metric ties by the output type's compareTo: ascending keys, or for a LONG column with
+// output type STRING the decimal text's String.compareTo (long_text_key).
+static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in,
+                           const dg_topn_opts* opts, int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
   if (!q || !t || !in || !out_n || (in->n_lists > 0 && (!in->list_n || !in->keys || !in->values)))
     return set_error(DG_ERR_ARG, "null argument");
+  const int32_t out_type = opts && opts->output_type ? opts->output_type : DG_COL_STRING;
+  if (out_type != DG_COL_STRING && !is_numeric_type(out_type))
+    return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: output type %d", t->dimension ? t->dimension : "", out_type);
   AggPlan plan;
   int rc = make_plan(q, &plan);
   if (rc) return rc;
@@ -3872,13 +4029,39 @@ int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, c
   const int na = plan.n, mk = plan.kind[t->metric_agg], nl = in->n_lists;
   // the dimension column of every list's segment, resolved once (segment mode)
   std::vector<const Column*> lcol(nl > 0 ? nl : 1, nullptr);
+  int num_type = 0;  // segment mode: DG_COL_* of a numeric dimension
   if (segs) {
     const std::string dim = t->dimension ? t->dimension : "";
+    int n_num = 0, n_other = 0;
     for (int l = 0; l < nl; ++l) {
+      if (in->list_n[l] < 0) continue;  // (no cursor: the segment's column is not looked at)
       const Column* c = reinterpret_cast<const Segment*>(segs[l])->find(dim);
-      lcol[l] = (c && c->type == DG_COL_STRING) ? c : nullptr;
+      if (c && is_numeric_type(c->type)) {
+        if (num_type && num_type != c->type)
+          return set_error(DG_ERR_UNSUPPORTED, "topN column %s has different numeric types in the lists' segments", dim.c_str());
+        num_type = c->type;
+        ++n_num;
+        if (!c->nd_ready) return set_error(DG_ERR_ARG, "numeric dimension %s has no encoding", dim.c_str());
+        for (int e = 0; e < in->list_n[l]; ++e) {
+          const int64_t id = in->keys[(int64_t)l * in->stride + e];
+          if (id < 0 || id >= c->nd_card) return set_error(DG_ERR_ARG, "id %lld of list %d is not below the cardinality of %s", (long long)id, l, dim.c_str());
+        }
+        lcol[l] = c;
+      } else {
+        ++n_other;
+        lcol[l] = (c && c->type == DG_COL_STRING) ? c : nullptr;
+      }
     }
+    if (n_num && n_other)
+      return set_error(DG_ERR_UNSUPPORTED, "topN column %s is numeric in %d of the lists' segments and a string or missing in %d",
+                       dim.c_str(), n_num, n_other);
+    if (!n_num && n_other && out_type != DG_COL_STRING)
+      return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: numeric output type on a string column", dim.c_str());
+    if (num_type && out_type != num_type && !(num_type == DG_COL_LONG && out_type == DG_COL_STRING))
+      return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: output type %d on a column of type %d", dim.c_str(), out_type, num_type);
   }
+  const bool text_order = num_type == DG_COL_LONG && out_type == DG_COL_STRING;
+  auto num_key = [&](int32_t list, int64_t id) { return lcol[list]->nd_host[(size_t)id]; };
   struct Ent {
     int32_t list;
     int64_t key;
@@ -3901,6 +4084,11 @@ int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, c
   };
   auto dim_cmp = [&](const Ent& a, const Ent& b) -> int {
     if (!segs) return a.key < b.key ? -1 : (a.key > b.key ? 1 : 0);
+    if (num_type) {
+      const int64_t x = num_key(a.list, a.key), y = num_key(b.list, b.key);
+      if (text_order) return long_text_less(x, y) ? -1 : (long_text_less(y, x) ? 1 : 0);
+      return x < y ? -1 : (x > y ? 1 : 0);
+    }
     std::string_view sa, sb;
     const bool an = value_of(a, &sa), bn = value_of(b, &sb);
     if (an || bn) return an == bn ? 0 : (an ? -1 : 1);
@@ -3941,12 +4129,14 @@ int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, c
   // hit is confirmed on the bytes
   auto ident = [&](const Ent& e) -> uint64_t {
     if (!segs) return (uint64_t)e.key * 0x9e3779b97f4a7c15ull;
+    if (num_type) return (uint64_t)num_key(e.list, e.key) * 0x9e3779b97f4a7c15ull;
     const Column* c = lcol[e.list];
     if (!c || e.key < 0 || e.key >= (int64_t)c->dict.size()) return kNullValueHash;
     return c->dict_hash[e.key];
   };
   auto same = [&](const Ent& a, const Ent& b) -> bool {
     if (!segs) return a.key == b.key;
+    if (num_type) return num_key(a.list, a.key) == num_key(b.list, b.key);
     std::string_view sa, sb;
     const bool an = value_of(a, &sa), bn = value_of(b, &sb);
     return an == bn && (an || sa == sb);
@@ -4024,6 +4214,16 @@ int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, c
   return DG_OK;
 }
 
+int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in, int32_t* out_n,
+                  int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
+  return topn_merge_impl(segs, q, t, in, nullptr, out_n, out_list, out_keys, out_values);
+}
+
+int dg_topn_merge_opts(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in,
+                       const dg_topn_opts* opts, int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
+  return topn_merge_impl(segs, q, t, in, opts, out_n, out_list, out_keys, out_values);
+}
+
 // ------------------------------------------------------------------------------------------------
 // groupBy (v2): per-segment grouping + GroupByMergingQueryRunnerV2 merge, as one device-wide sort
 // ------------------------------------------------------------------------------------------------
@@ -4061,11 +4261,12 @@ static int dim_kind(Segment* const* segs, int n, const char* dim, int32_t out_ty
   return DG_OK;
 }
 
-// The long-dimension encoding of one (segment, LONG column), built on the device (dg_numdim.hip) by the
-// first groupBy that groups by the column and kept in the Column like its other query-independent
-// indexes (tix_*, vcnt):
-//   1. the column's VIEW_LONG view through the ordinary decode path (any codec / long encoding / a
-//      segment from rows), 2. its min and max, 3. words (v - min), 4. the radix sort over
+// The numeric-dimension encoding of one (segment, LONG / FLOAT / DOUBLE column), built on the device
+// (dg_numdim.hip) by the first groupBy or topN over the column and kept in the Column like its other
+// query-independent indexes (tix_*, vcnt). A row's value v is its key (the long; the order-preserving
+// fold of a float's / double's canonical bits, nd_value):
+//   1. the column's VIEW_LONG / VIEW_FLOAT / VIEW_DOUBLE view through the ordinary decode path (any codec /
+//      long encoding / a segment from rows), 2. its min and max, 3. words (v - min), 4. the radix sort over
 //      bits_for(max - min) key bits (none when max == min), 5. run heads counted per tile and scanned,
 //      6. the cardinality read back, nd_vals allocated at exactly that size and filled (run heads + min),
 //      7. nd_ids[r] = lower bound of v[r] in nd_vals; nd_vals read back once.
@@ -4073,13 +4274,13 @@ static int dim_kind(Segment* const* segs, int n, const char* dim, int32_t out_ty
 // word buffers, control memory) is the call's and is the caller's again afterwards. The column takes the
 // buffers only when every step succeeded: a failed or interrupted build leaves it without an encoding and
 // the next call builds again. cancel / timeout are checked between the launch groups and polled in the waits.
-static int build_long_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c, hipStream_t st) {
+static int build_num_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c, hipStream_t st) {
   if (c->nd_ready) return DG_OK;
   const int64_t nrows = seg->nrows;
   if (c->data.total != nrows)
     return set_error(DG_ERR_FORMAT, "column %s holds %d rows, its segment %lld", c->name.c_str(), c->data.total, (long long)nrows);
   // (one block of 4-byte ids: the id loaders form a row's byte offset in 32 bits)
-  if (nrows >= (1ll << 30)) return set_error(DG_ERR_UNSUPPORTED, "groupBy on LONG column %s of %lld rows", c->name.c_str(), (long long)nrows);
+  if (nrows >= (1ll << 30)) return set_error(DG_ERR_UNSUPPORTED, "numeric dimension %s of %lld rows", c->name.c_str(), (long long)nrows);
   DevBuf ids, vals, ptr;
   std::vector<int64_t> host;
   int64_t card = 0;
@@ -4183,7 +4384,7 @@ static int build_long_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c
 // local id -> merged id table in HBM. A segment without the column contributes the null value.
 //
 // A long dimension (LONG in every segment, dim_kind): the segments' sorted value lists (Column::nd_host,
-// build_long_dim) merge the same way into MergedDict::longs, ordered by the output type — DG_COL_LONG:
+// build_num_dim) merge the same way into MergedDict::longs, ordered by the output type — DG_COL_LONG:
 // ascending, the order LongRowBasedKeySerdeHelper compares grouping keys in (Longs.compare,
 // RowBasedGrouperHelper.java:1389-1437); DG_COL_STRING: the rows carry String.valueOf(value)
 // (convertRowTypesToOutputTypes, GroupByQueryEngineV2.java:689-698) and GroupByMergingQueryRunnerV2
@@ -4490,14 +4691,14 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   Interrupt intr(q, t0);
   cs->intr = &intr;
   hipStream_t st = ctx->stream;
-  // the long dimensions' encodings this call is the first to need (build_long_dim): each build ends with
+  // the long dimensions' encodings this call is the first to need (build_num_dim): each build ends with
   // a wait, after which its scratch is the call's again
   for (int d = 0; d < nd; ++d) {
     if (!dim_long[d]) continue;
     for (int i = 0; i < n; ++i) {
       Column* c = sv[i]->find(gb->dimensions[d]);
       if (c->nd_ready) continue;
-      rc = build_long_dim(ctx, cs, sv[i], c, st);
+      rc = build_num_dim(ctx, cs, sv[i], c, st);
       if (rc) return rc;
       cs->reset();
       cs->intr = &intr;
@@ -6538,18 +6739,46 @@ extern "C" int dg_debug_groupby_totals_source(dg_context* c, int32_t* source) {
   return DG_OK;
 }
 
-extern "C" int dg_debug_long_dim_info(dg_segment* s, const char* column, int32_t* built, int64_t* cardinality,
-                                      int64_t* device_bytes, double* build_ms) {
+// the shared body of dg_debug_long_dim_info and dg_segment_numeric_dim_info
+static int numeric_dim_info(dg_segment* s, const char* column, bool long_only, int32_t* built, int64_t* cardinality,
+                            int64_t* device_bytes, double* build_ms) {
   Segment* seg = reinterpret_cast<Segment*>(s);
   if (!seg || !column) return set_error(DG_ERR_ARG, "null argument");
   const Column* c = seg->find(column);
   if (!c) return set_error(DG_ERR_NOT_FOUND, "no column %s", column);
-  if (c->type != DG_COL_LONG) return set_error(DG_ERR_ARG, "%s is not a LONG column", column);
+  if (long_only ? c->type != DG_COL_LONG : !is_numeric_type(c->type))
+    return set_error(DG_ERR_ARG, "%s is not a %s column", column, long_only ? "LONG" : "numeric");
   std::lock_guard<std::mutex> g(seg->ctx->mu);
   if (built) *built = c->nd_ready ? 1 : 0;
   if (cardinality) *cardinality = c->nd_ready ? c->nd_card : 0;
   if (device_bytes) *device_bytes = c->nd_ready ? (int64_t)(c->nd_ids.n + c->nd_vals.n) : 0;
   if (build_ms) *build_ms = c->nd_ready ? c->nd_build_ms : 0.0;
+  return DG_OK;
+}
+
+extern "C" int dg_debug_long_dim_info(dg_segment* s, const char* column, int32_t* built, int64_t* cardinality,
+                                      int64_t* device_bytes, double* build_ms) {
+  return numeric_dim_info(s, column, true, built, cardinality, device_bytes, build_ms);
+}
+
+extern "C" int dg_segment_numeric_dim_info(dg_segment* s, const char* column, int32_t* built, int64_t* cardinality,
+                                           int64_t* device_bytes, double* build_ms) {
+  return numeric_dim_info(s, column, false, built, cardinality, device_bytes, build_ms);
+}
+
+extern "C" int dg_segment_numeric_dim_values(dg_segment* s, const char* column, const int32_t* ids, int32_t n, uint64_t* out) {
+  Segment* seg = reinterpret_cast<Segment*>(s);
+  if (!seg || !column || n < 0 || (n > 0 && (!ids || !out))) return set_error(DG_ERR_ARG, "null argument");
+  const Column* c = seg->find(column);
+  if (!c) return set_error(DG_ERR_NOT_FOUND, "no column %s", column);
+  if (!is_numeric_type(c->type)) return set_error(DG_ERR_ARG, "%s is not a numeric column", column);
+  std::lock_guard<std::mutex> g(seg->ctx->mu);
+  if (!c->nd_ready) return set_error(DG_ERR_ARG, "numeric dimension %s has no encoding yet", column);
+  for (int32_t k = 0; k < n; ++k) {
+    if (ids[k] < 0 || ids[k] >= c->nd_card)
+      return set_error(DG_ERR_ARG, "id %d of %s is not below the cardinality %lld", ids[k], column, (long long)c->nd_card);
+    out[k] = nd_key_bits(c->type, c->nd_host[(size_t)ids[k]]);
+  }
   return DG_OK;
 }
 

@@ -448,18 +448,35 @@ struct Column {
   DevBuf vcnt;
   bool vcnt_ready = false;
   bool vcnt_never = false;
-  // long-dimension encoding of a LONG column (built on the device by the first groupBy that groups by the
-  // column, then reused; dg_numdim.hip): nd_vals = int64[nd_card], the column's distinct values ascending
-  // (nd_host: its host copy, read back once); nd_ids = uint32[rows], row r's index into nd_vals, viewed by
-  // the groupBy as ONE block of little-endian 4-byte ids (nd_ptr: the one-entry block table in HBM,
-  // log2_per = kNdLog2Per). Ready only after a build that ran to its end.
+  // numeric-dimension encoding of a LONG, FLOAT or DOUBLE column (built on the device by the first groupBy
+  // or topN over the column, then reused; dg_numdim.hip): nd_vals = int64[nd_card], the column's distinct
+  // keys ascending (a LONG's key is the value, a FLOAT's / DOUBLE's the order-preserving fold of its
+  // canonical bits, nd_key_bits; nd_host: its host copy, read back once); nd_ids = uint32[rows], row r's
+  // index into nd_vals, viewed by the groupBy and the topN as ONE block of little-endian 4-byte ids
+  // (nd_ptr: the one-entry block table in HBM, log2_per = kNdLog2Per). Ready only after a build that ran
+  // to its end. nd_text: LONG only, position of every id in String.compareTo order of the decimal text
+  // (long_text_key), derived on the host by the first topN that needs it.
   DevBuf nd_vals, nd_ids, nd_ptr;
   std::vector<int64_t> nd_host;
+  std::vector<int32_t> nd_text;
   int64_t nd_card = 0;
   double nd_build_ms = 0;
   bool nd_ready = false;
 };
 constexpr int kNdLog2Per = 31;  // rows of a segment are int32: every row lies in block 0
+
+inline bool is_numeric_type(int type) { return type == DG_COL_LONG || type == DG_COL_FLOAT || type == DG_COL_DOUBLE; }
+
+// The value of a numeric-dimension key in the aggregate slot encoding (int64 / double bits / float32 bits
+// in the low 4 bytes): the fold b ^ ((b >> 31 or 63) & 0x7fff…) is its own inverse.
+inline uint64_t nd_key_bits(int type, int64_t key) {
+  if (type == DG_COL_DOUBLE) return (uint64_t)(key ^ ((key >> 63) & 0x7fffffffffffffffll));
+  if (type == DG_COL_FLOAT) {
+    const int32_t k = (int32_t)key;
+    return (uint64_t)(uint32_t)(k ^ ((k >> 31) & 0x7fffffff));
+  }
+  return (uint64_t)key;
+}
 
 // Merged dictionary of one dimension over a set of segments (the union of their sorted
 // dictionaries in Java String order, nulls first) + each segment's local id -> merged id table in

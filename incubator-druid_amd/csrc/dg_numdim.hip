@@ -1,8 +1,16 @@
-// dg_numdim.hip — HIP kernels (gfx950 / CDNA4, wave64) of the long-dimension encoding: a LONG column
-// becomes what a dictionary-encoded string column is, a sorted value list (nd_vals) plus one id per row
-// (nd_ids), so the groupBy groups by it as by any dimension (the reference keys such a dimension by the
-// long itself: LongGroupByColumnSelectorStrategy, GroupByQueryEngineV2.java:235-260). Built once per
-// (segment, column) by the first groupBy over the column (Column::nd_*, dg_engine.cpp build_long_dim).
+// dg_numdim.hip — HIP kernels (gfx950 / CDNA4, wave64) of the numeric-dimension encoding: a LONG, FLOAT
+// or DOUBLE column becomes what a dictionary-encoded string column is, a sorted value list (nd_vals) plus
+// one id per row (nd_ids), so the groupBy (LONG) and the topN (all three) run over it as over any
+// dimension (the reference keys such a dimension by the long itself, Float.floatToIntBits or
+// Double.doubleToLongBits: LongGroupByColumnSelectorStrategy, GroupByQueryEngineV2.java:235-260;
+// NumericTopNColumnSelectorStrategy.java:81-151). Built once per (segment, column) by the first groupBy
+// or topN over the column (Column::nd_*, dg_engine.cpp build_num_dim).
+//
+// A row's value is its signed 64-bit key (nd_value): the long itself, or for a float / double the
+// canonical bits b (every NaN -> 0x7fc00000 / 0x7ff8000000000000, as floatToIntBits / doubleToLongBits
+// give) folded to b ^ ((b >> 31 or 63) & 0x7fff…), widened to int64. Ascending keys are Float.compare /
+// Double.compare order (-0.0 < 0.0, NaN greatest), equal keys are equal bits, and the fold is its own
+// inverse, so nd_vals holds keys and the export folds them back.
 //
 //   k_nd_minmax        the column's smallest and largest value                      8 B read per row
 //   k_nd_words         word[r] = (uint64)(v[r] - min): the sort's keys              8 B read + 8 B written
@@ -27,17 +35,30 @@ constexpr int kNdT = 256;                   // threads per workgroup
 constexpr int kNdPer = kSortTile / kNdT;    // elements per thread of a tile
 static_assert(kNdPer * kNdT == kSortTile, "whole tiles");
 
+template <int KIND>
 __device__ __forceinline__ int64_t nd_value(const ColView& v, int64_t r) {
-  return *reinterpret_cast<const int64_t*>(cv_ptr(v, r));
+  const uint8_t* p = cv_ptr(v, r);
+  if (KIND == VIEW_FLOAT) {
+    const float x = *reinterpret_cast<const float*>(p);
+    const int32_t b = x != x ? 0x7fc00000 : __float_as_int(x);
+    return (int64_t)(b ^ ((b >> 31) & 0x7fffffff));
+  }
+  if (KIND == VIEW_DOUBLE) {
+    const double x = *reinterpret_cast<const double*>(p);
+    const int64_t b = x != x ? 0x7ff8000000000000ll : (int64_t)__double_as_longlong(x);
+    return b ^ ((b >> 63) & 0x7fffffffffffffffll);
+  }
+  return *reinterpret_cast<const int64_t*>(p);
 }
 
 // mm[0] = min, mm[1] = max over the rows, as order-preserving unsigned keys (value ^ sign); the host
 // initialises mm to {~0, 0}. One atomic pair per workgroup.
+template <int KIND>
 __global__ __launch_bounds__(kNdT) void k_nd_minmax(ColView v, int64_t nrows, unsigned long long* __restrict__ mm) {
   __shared__ uint64_t s_lo[kNdT / 64], s_hi[kNdT / 64];
   uint64_t lo = ~0ull, hi = 0ull;
   for (int64_t r = (int64_t)blockIdx.x * kNdT + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * kNdT) {
-    const uint64_t k = (uint64_t)nd_value(v, r) ^ kSign;
+    const uint64_t k = (uint64_t)nd_value<KIND>(v, r) ^ kSign;
     lo = k < lo ? k : lo;
     hi = k > hi ? k : hi;
   }
@@ -67,10 +88,11 @@ __global__ __launch_bounds__(kNdT) void k_nd_minmax(ColView v, int64_t nrows, un
 }
 
 // The subtraction wraps in 64 bits and is exact for every range (Long.MIN_VALUE .. Long.MAX_VALUE gives
-// words 0 .. 2^64 - 1): the words order like the values.
+// words 0 .. 2^64 - 1): the words order like the values (keys).
+template <int KIND>
 __global__ __launch_bounds__(kNdT) void k_nd_words(ColView v, int64_t nrows, int64_t vmin, uint64_t* __restrict__ words) {
   for (int64_t r = (int64_t)blockIdx.x * kNdT + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * kNdT)
-    words[r] = (uint64_t)nd_value(v, r) - (uint64_t)vmin;
+    words[r] = (uint64_t)nd_value<KIND>(v, r) - (uint64_t)vmin;
 }
 
 // A head is a word that differs from its predecessor; a tile's first word is compared with the last word
@@ -129,10 +151,11 @@ __global__ __launch_bounds__(kNdT) void k_nd_unique_emit(const uint64_t* __restr
 }
 
 // ids[r] = index of v[r] in vals (every row's value is in the list: the lower bound is its position)
+template <int KIND>
 __global__ __launch_bounds__(kNdT) void k_nd_encode(ColView v, int64_t nrows, const int64_t* __restrict__ vals,
                                                     uint32_t card, uint32_t* __restrict__ ids) {
   for (int64_t r = (int64_t)blockIdx.x * kNdT + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * kNdT) {
-    const int64_t x = nd_value(v, r);
+    const int64_t x = nd_value<KIND>(v, r);
     uint32_t lo = 0, len = card;
     while (len > 0) {
       const uint32_t h = len >> 1;
@@ -151,12 +174,18 @@ static unsigned nd_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max
 
 void launch_nd_minmax(const ColView& v, int64_t nrows, unsigned long long* mm, hipStream_t s) {
   if (nrows <= 0) return;
-  hipLaunchKernelGGL(k_nd_minmax, dim3(nd_grid(nrows)), dim3(kNdT), 0, s, v, nrows, mm);
+  const dim3 g(nd_grid(nrows)), b(kNdT);
+  if (v.kind == VIEW_FLOAT) hipLaunchKernelGGL(k_nd_minmax<VIEW_FLOAT>, g, b, 0, s, v, nrows, mm);
+  else if (v.kind == VIEW_DOUBLE) hipLaunchKernelGGL(k_nd_minmax<VIEW_DOUBLE>, g, b, 0, s, v, nrows, mm);
+  else hipLaunchKernelGGL(k_nd_minmax<VIEW_LONG>, g, b, 0, s, v, nrows, mm);
 }
 
 void launch_nd_words(const ColView& v, int64_t nrows, int64_t vmin, uint64_t* words, hipStream_t s) {
   if (nrows <= 0) return;
-  hipLaunchKernelGGL(k_nd_words, dim3(nd_grid(nrows)), dim3(kNdT), 0, s, v, nrows, vmin, words);
+  const dim3 g(nd_grid(nrows)), b(kNdT);
+  if (v.kind == VIEW_FLOAT) hipLaunchKernelGGL(k_nd_words<VIEW_FLOAT>, g, b, 0, s, v, nrows, vmin, words);
+  else if (v.kind == VIEW_DOUBLE) hipLaunchKernelGGL(k_nd_words<VIEW_DOUBLE>, g, b, 0, s, v, nrows, vmin, words);
+  else hipLaunchKernelGGL(k_nd_words<VIEW_LONG>, g, b, 0, s, v, nrows, vmin, words);
 }
 
 void launch_nd_unique_count(const uint64_t* words, int64_t n, uint32_t* tile_cnt, unsigned long long* info, hipStream_t s) {
@@ -174,7 +203,10 @@ void launch_nd_unique_emit(const uint64_t* words, int64_t n, const uint32_t* til
 
 void launch_nd_encode(const ColView& v, int64_t nrows, const int64_t* vals, uint32_t card, uint32_t* ids, hipStream_t s) {
   if (nrows <= 0 || card == 0) return;
-  hipLaunchKernelGGL(k_nd_encode, dim3(nd_grid(nrows)), dim3(kNdT), 0, s, v, nrows, vals, card, ids);
+  const dim3 g(nd_grid(nrows)), b(kNdT);
+  if (v.kind == VIEW_FLOAT) hipLaunchKernelGGL(k_nd_encode<VIEW_FLOAT>, g, b, 0, s, v, nrows, vals, card, ids);
+  else if (v.kind == VIEW_DOUBLE) hipLaunchKernelGGL(k_nd_encode<VIEW_DOUBLE>, g, b, 0, s, v, nrows, vals, card, ids);
+  else hipLaunchKernelGGL(k_nd_encode<VIEW_LONG>, g, b, 0, s, v, nrows, vals, card, ids);
 }
 
 }  // namespace dg

@@ -189,7 +189,14 @@ def gather_topn(dist, query: Q.TopNQuery, raw: "R.TopNRaw", gdict: GlobalDiction
     (dg_topn_merge, global-id mode) and returns the result; other ranks return None.
 
     The reference's approximation is kept exactly: each segment contributes its own top
-    max(threshold, 1000) list and the fold truncates to the query threshold after every step."""
+    max(threshold, 1000) list and the fold truncates to the query threshold after every step.
+
+    A numeric topN dimension (a DimensionSpec output type other than STRING, or a LONG / FLOAT / DOUBLE
+    column) is refused: its result ids index per-segment value lists, which have no cluster-wide
+    dictionary here."""
+    if query.dimension_type != "STRING" or any(s.column_type(query.dimension) in R._NUMERIC_COLS
+                                               for s in (segments or getattr(raw, "segments", None) or [])):
+        raise R.N.UnsupportedQuery(2, f"topN on numeric dimension {query.dimension} across processes")
     torch, _ = _torch()
     dev = _device(dist)
     K = raw.K

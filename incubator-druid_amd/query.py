@@ -771,16 +771,24 @@ class TimeseriesQuery(BaseQuery):
 
 @dataclass
 class TopNQuery(BaseQuery):
+    """dimension: the column's name; it may be given as a DefaultDimensionSpec, whose outputType
+    (query/dimension/DefaultDimensionSpec.java:68-78, STRING when absent) becomes dimension_type."""
     dimension: str = ""
     metric: Any = None
     threshold: int = 10
+    dimension_type: str = "STRING"
 
     def __post_init__(self):
         super().__post_init__()
         if isinstance(self.dimension, dict):
             if self.dimension.get("extractionFn") is not None:
                 raise ValueError("extraction functions are out of scope")
+            if self.dimension.get("outputType") is not None:
+                self.dimension_type = self.dimension["outputType"]
             self.dimension = self.dimension["dimension"]
+        self.dimension_type = str(self.dimension_type).upper()
+        if self.dimension_type not in DIMENSION_OUTPUT_TYPES:
+            raise ValueError(f"unknown outputType {self.dimension_type!r}")
         self.metric = TopNMetricSpec.of(self.metric)
         if self.metric.type in ("numeric", "inverted") and self.metric.metric not in {a.name for a in self.aggregations}:
             raise ValueError("topN metric must name an aggregator")
@@ -797,7 +805,10 @@ class TopNQuery(BaseQuery):
 
     def to_json(self):
         js = self._base_json("topN")
-        js.update({"dimension": self.dimension, "metric": self.metric.to_json(), "threshold": self.threshold})
+        dim = self.dimension
+        if self.dimension_type != "STRING":
+            dim = {"type": "default", "dimension": dim, "outputName": dim, "outputType": self.dimension_type}
+        js.update({"dimension": dim, "metric": self.metric.to_json(), "threshold": self.threshold})
         return js
 
 

@@ -234,6 +234,53 @@ def _java_key(s: Optional[str]):
     return (0, b"") if s is None else (1, s.encode("utf-16-be", "surrogatepass"))
 
 
+_NUMERIC_COLS = (N.COL_LONG, N.COL_FLOAT, N.COL_DOUBLE)
+_OUT_TYPES = {"STRING": N.COL_STRING, "LONG": N.COL_LONG, "FLOAT": N.COL_FLOAT, "DOUBLE": N.COL_DOUBLE}
+
+
+def numeric_key(v: float, single: bool = False) -> int:
+    """The order-preserving signed key of a float's canonical bits (Float.floatToIntBits /
+    Double.doubleToLongBits folded with b ^ ((b >> 31 or 63) & 0x7fff…)): ascending keys are Float.compare /
+    Double.compare order (-0.0 < 0.0, NaN greatest). The fold is its own inverse (numeric_key_value)."""
+    if single:
+        b = 0x7fc00000 if v != v else int(np.array([v], dtype=np.float32).view(np.int32)[0])
+        return b ^ ((b >> 31) & 0x7fffffff)
+    b = 0x7ff8000000000000 if v != v else int(np.array([v], dtype=np.float64).view(np.int64)[0])
+    return b ^ ((b >> 63) & 0x7fffffffffffffff)
+
+
+def numeric_key_value(key: int, single: bool = False) -> float:
+    if single:
+        b = key ^ ((key >> 31) & 0x7fffffff)
+        return float(np.array([b], dtype=np.int32).view(np.float32)[0])
+    b = key ^ ((key >> 63) & 0x7fffffffffffffff)
+    return float(np.array([b], dtype=np.int64).view(np.float64)[0])
+
+
+def _dim_tie_key(v):
+    """dimValue.compareTo of the builder's comparator (TopNNumericResultBuilder.java:94-107): String.compareTo
+    with nulls first, Long.compareTo, Double / Float.compareTo (a float32 widens exactly)."""
+    if v is None or isinstance(v, str):
+        return _java_key(v)
+    if isinstance(v, float):
+        return (1, numeric_key(v))
+    return (1, int(v))
+
+
+def _text_sort_key(query: Q.TopNQuery):
+    """The dimension-ordered spec's comparator as a sort key over the entries' dimension values: over the
+    strings themselves, or for a numeric output type over Objects.toString of the value."""
+    key = O.sort_key(query.metric.ordering, query.metric.inverted)
+    if query.dimension_type == "STRING":
+        return key
+    return lambda v: key(_dim_text(v))
+
+
+def _dim_text(v):
+    """Objects.toString of a dimension value (TopNLexicographicResultBuilder.java:66-125); null stays null."""
+    return v if v is None or isinstance(v, str) else str(v)
+
+
 class _HeapItem:
     __slots__ = ("mk", "dk", "entry")
 
@@ -256,6 +303,8 @@ class TopNResultBuilder:
         self.inverted = spec.type == "inverted"
         self.agg = agg
         self.threshold = threshold
+        # (a string dimension's values: String.compareTo, nulls first; numeric output types: their compareTo)
+        self.dim_key = _java_key if query.dimension_type == "STRING" else _dim_tie_key
         self.heap: List[_HeapItem] = []
 
     def _mk(self, v):
@@ -265,7 +314,7 @@ class TopNResultBuilder:
     def add(self, entry: Dict):
         mk = self._mk(entry[self.metric])
         if len(self.heap) < self.threshold or self.heap[0].mk < mk:
-            heapq.heappush(self.heap, _HeapItem(mk, _java_key(entry[self.dim]), entry))
+            heapq.heappush(self.heap, _HeapItem(mk, self.dim_key(entry[self.dim]), entry))
         if len(self.heap) > self.threshold:
             heapq.heappop(self.heap)
 
@@ -346,7 +395,7 @@ class LexicographicResultBuilder:
     def __init__(self, query: Q.TopNQuery, threshold: int):
         spec = query.metric
         self.dim = query.dimension
-        self.key = _memo_key(O.sort_key(spec.ordering, spec.inverted))
+        self.key = _memo_key(_text_sort_key(query))
         self.cmp = _key_cmp(self.key)
         self.threshold = threshold
         self.stop = spec.previous_stop
@@ -388,11 +437,50 @@ class _Rev:
 class TopNRaw:
     """dg_topn_run output for segments of one device: list L = i * bcap + b (segment i, cursor b; bcap = 1
     for ALL granularity) has `cnt[L]` entries (-1 = no cursor), entry j at L * K + j of `ids`
-    (segment-local dictionary ids) and `vals` (n_aggs slots); `ts[L]` is the list's result timestamp."""
+    (segment-local dictionary ids, or ids into a numeric column's value list) and `vals` (n_aggs slots);
+    `ts[L]` is the list's result timestamp; `cut_ties[L]` counts the values of a numeric dimension whose
+    metric equals the list's last entry's and that are not in the list (dg_topn_opts.out_cut_ties: nonzero
+    where the reference's pick among them depends on its hash map's iteration order)."""
 
-    def __init__(self, segments, cnt, ids, vals, K, ts, bcap=1):
+    def __init__(self, segments, cnt, ids, vals, K, ts, bcap=1, cut_ties=None):
         self.segments, self.cnt, self.ids, self.vals, self.K, self.ts = segments, cnt, ids, vals, K, ts
         self.bcap = bcap
+        self.numeric = cut_ties is not None  # the dimension is numeric (then the counts were asked for)
+        self._cut_ties = cut_ties
+
+    @property
+    def cut_ties(self) -> np.ndarray:
+        if self._cut_ties is None:  # a string dimension: nothing is cut arbitrarily
+            self._cut_ties = np.zeros(len(self.cnt), dtype=np.int32)
+        return self._cut_ties
+
+
+def _numeric_dimension(segments: Sequence[GpuSegment], query: Q.TopNQuery) -> bool:
+    """The topN runs over a numeric dimension: a numeric output type, or a LONG / FLOAT / DOUBLE column."""
+    if query.dimension_type != "STRING":
+        return True
+    dim = query.dimension
+    for s in segments:
+        if s.column_type(dim) in _NUMERIC_COLS:
+            return True
+    return False
+
+
+def _topn_opts(query: Q.TopNQuery, cut_ties: Optional[np.ndarray] = None) -> N.dg_topn_opts:
+    o = N.dg_topn_opts()
+    o.output_type = _OUT_TYPES[query.dimension_type]
+    o.out_cut_ties = cut_ties.ctypes.data if cut_ties is not None else None
+    return o
+
+
+def topn_dim_values(seg: GpuSegment, query: Q.TopNQuery, ids) -> List:
+    """The dimension values of result ids: dictionary strings, or for a numeric column the values converted
+    to the dimension's output type (convertAggregatorStoreKeyToColumnValue): int, float, or the decimal str."""
+    dim = query.dimension
+    if seg.column_type(dim) not in _NUMERIC_COLS:
+        return [seg.dim_value(dim, int(x)) for x in ids]
+    vals = seg.numeric_dim_values(dim, ids).tolist()
+    return [str(v) for v in vals] if query.dimension_type == "STRING" else vals
 
 
 def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence[GpuSegment]] = None):
@@ -418,7 +506,8 @@ def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence
                 order = seg.dim_order(query.dimension, spec.ordering, spec.inverted)
                 if order is not None:
                     mins[i] = order.min_rank(spec.previous_stop)
-                else:  # missing dimension: its one value is null, never after a previousStop
+                else:  # missing dimension: its one value is null, never after a previousStop (a numeric
+                    #    column: the engine derives the ranks itself and refuses a previousStop)
                     mins[i] = 0 if spec.previous_stop is None else 1
             t.min_rank = mins.ctypes.data
             keep.append(mins)
@@ -433,15 +522,17 @@ def _check_topn(query: Q.TopNQuery):
     pass
 
 
-def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional[RunStats] = None) -> TopNRaw:
-    """One batched dg_topn_run over segments that share a device (PooledTopNAlgorithm +
-    TopNNumericResultBuilder per segment, threshold max(threshold, minTopNThreshold))."""
+def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional[RunStats] = None,
+             cancel: Optional[ctypes.c_int32] = None) -> TopNRaw:
+    """One batched dg_topn_run_opts over segments that share a device (PooledTopNAlgorithm, or over a numeric
+    dimension DimExtractionTopNAlgorithm, + TopNNumericResultBuilder per segment, threshold
+    max(threshold, minTopNThreshold)). cancel: a flag another thread may set (DG_ERR_INTERRUPTED)."""
     _check_topn(query)
     if len(_group_by_device(segments)) != 1:
         raise ValueError("topn_raw: segments must share one device")
     na = len(query.aggregations)
     K = query.segment_threshold
-    scan, keep = N.make_scan(query, Q, segments=segments)
+    scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
     t, keep_t = _topn_struct(query, K, segments)
     n = len(segments)
     bcap = _bucket_cap(segments, query)
@@ -451,16 +542,22 @@ def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
     bt = np.zeros(n * bcap, dtype=np.int64)
     t.bucket_cap = bcap
     t.out_bucket_time = bt.ctypes.data
+    cut = opts = None  # (a string dimension: dg_topn_run_opts without options is dg_topn_run)
+    if _numeric_dimension(segments, query):
+        cut = np.zeros(n * bcap, dtype=np.int32)
+        opts = ctypes.byref(_topn_opts(query, cut))
     m = N.dg_metrics()
-    N.check(N.lib().dg_topn_run(_handles(segments), n, ctypes.byref(scan), ctypes.byref(t), cnt.ctypes.data,
-                                ids.ctypes.data, vals.ctypes.data, ctypes.byref(m)))
+    N.check(N.lib().dg_topn_run_opts(_handles(segments), n, ctypes.byref(scan), ctypes.byref(t), opts,
+                                     cnt.ctypes.data, ids.ctypes.data, vals.ctypes.data, ctypes.byref(m)))
     if stats is not None:
         stats.add(m)
+        if cut is not None:
+            stats.calls[-1]["topn_cut_ties"] = int(cut.sum())
     if query.granularity.is_all:  # the cursor's time: start of the segment's part of the interval
         ts = np.array([max(query.interval[0], s.min_time) for s in segments], dtype=np.int64)
     else:
         ts = bt
-    return TopNRaw(list(segments), cnt, ids, vals, K, ts, bcap)
+    return TopNRaw(list(segments), cnt, ids, vals, K, ts, bcap, cut)
 
 
 def topn_merge_raw(query: Q.TopNQuery, cnt: np.ndarray, keys: np.ndarray, vals: np.ndarray, K: int,
@@ -498,8 +595,10 @@ def topn_merge_raw(query: Q.TopNQuery, cnt: np.ndarray, keys: np.ndarray, vals: 
     hs = None
     if handles is not None:
         hs = (ctypes.c_void_p * n)(*[handles[i] for i in order])
-    N.check(N.lib().dg_topn_merge(hs, ctypes.byref(scan), ctypes.byref(t), ctypes.byref(lists), ctypes.byref(out_n),
-                                  out_list.ctypes.data, out_keys.ctypes.data, out_vals.ctypes.data))
+    opts = None if query.dimension_type == "STRING" else ctypes.byref(_topn_opts(query))  # (None: output STRING)
+    N.check(N.lib().dg_topn_merge_opts(hs, ctypes.byref(scan), ctypes.byref(t), ctypes.byref(lists), opts,
+                                       ctypes.byref(out_n), out_list.ctypes.data, out_keys.ctypes.data,
+                                       out_vals.ctypes.data))
     k = out_n.value
     if k < 0:
         return None
@@ -546,7 +645,7 @@ def merge_dimension_lists(query: Q.TopNQuery, lists: Sequence[Tuple[int, int, "c
 
     if not tie_free:
         return fold(None)
-    key = O.sort_key(spec.ordering, spec.inverted)
+    key = _text_sort_key(query)
     heads = {value_of(j) for _, c, value_of, _ in lists for j in range(head(c, value_of))}
     keys = sorted(key(v) for v in heads)
     if any(a == b for a, b in zip(keys, keys[1:])):
@@ -565,6 +664,8 @@ def _merge_topn_dimension(query: Q.TopNQuery, segments: Sequence[GpuSegment], ra
     for i in live:
         seg, base = segments[i], i * K
         memo: Dict[int, Optional[str]] = {}  # (each entry's value looked up once)
+        if raw.numeric:
+            memo.update(enumerate(topn_dim_values(seg, query, raw.ids[base:base + int(raw.cnt[i])])))
 
         def value_of(j, seg=seg, base=base, memo=memo):
             v = memo.get(j, memo)
@@ -589,7 +690,10 @@ def run_topn(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
     if res is None:
         return []
     ts, lists, keys, slots = res
-    values = [segments[int(l)].dim_value(query.dimension, int(k)) for l, k in zip(lists, keys)]
+    if raw.numeric:
+        values = [topn_dim_values(segments[int(l)], query, [int(k)])[0] for l, k in zip(lists, keys)]
+    else:
+        values = [segments[int(l)].dim_value(query.dimension, int(k)) for l, k in zip(lists, keys)]
     return [Q.Result(ts, _topn_entries(query, values, slots))]
 
 
@@ -614,7 +718,7 @@ def topn_per_segment(segments: Sequence[GpuSegment], query: Q.TopNQuery,
                 if raw.cnt[L] < 0:  # no cursor: the segment does not overlap the interval / bucket
                     continue
                 c = int(raw.cnt[L])
-                values = [seg.dim_value(query.dimension, int(x)) for x in raw.ids[L * K:L * K + c]]
+                values = topn_dim_values(seg, query, raw.ids[L * K:L * K + c])
                 slots = raw.vals.reshape(-1, max(na, 1))[L * K:L * K + c, :na]
                 res.append(Q.Result(int(raw.ts[L]), _topn_entries(query, values, slots)))
             out[i] = res
@@ -629,13 +733,15 @@ def topn_binary_fn(query: Q.TopNQuery, r1: Optional[Q.Result], r2: Optional[Q.Re
         return r1
     dim = query.dimension
     ret: Dict = {}
+    # equals of the value object: a Float / Double by its bits (-0.0 is not 0.0, NaN is NaN)
+    by_bits = query.dimension_type in ("FLOAT", "DOUBLE")
     for v in r1.value:
-        ret[v[dim]] = v
+        ret[numeric_key(v[dim]) if by_bits else v[dim]] = v
     for v in r2.value:
-        k = v[dim]
+        k = numeric_key(v[dim]) if by_bits else v[dim]
         if k in ret:
             a = ret[k]
-            c = {dim: k}
+            c = {dim: v[dim]}
             for agg in query.aggregations:
                 c[agg.name] = agg.combine(a[agg.name], v[agg.name])
             ret[k] = c

@@ -111,6 +111,26 @@ class GpuSegment:
                                                ctypes.byref(nbytes), ctypes.byref(ms)))
         return {"built": bool(built.value), "cardinality": card.value, "device_bytes": nbytes.value, "build_ms": ms.value}
 
+    def numeric_dim_info(self, column: str) -> Dict:
+        """long_dim_info for any numeric column (dg_segment_numeric_dim_info): the encoding the first groupBy or
+        topN over the column builds."""
+        built, card, nbytes, ms = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        N.check(N.lib().dg_segment_numeric_dim_info(self.handle, column.encode(), ctypes.byref(built),
+                                                    ctypes.byref(card), ctypes.byref(nbytes), ctypes.byref(ms)))
+        return {"built": bool(built.value), "cardinality": card.value, "device_bytes": nbytes.value, "build_ms": ms.value}
+
+    def numeric_dim_values(self, column: str, ids) -> np.ndarray:
+        """The values of a numeric dimension's result ids (dg_segment_numeric_dim_values) in the column's own
+        type: int64, float32 or float64 (a NaN is the canonical one)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        out = np.zeros(len(ids), dtype=np.uint64)
+        N.check(N.lib().dg_segment_numeric_dim_values(self.handle, column.encode(), ids.ctypes.data, len(ids),
+                                                      out.ctypes.data))
+        t = self.column_type(column)
+        if t == N.COL_FLOAT:
+            return out.astype(np.uint32).view(np.float32)
+        return out.view(np.float64 if t == N.COL_DOUBLE else np.int64)
+
     def cardinality(self, dim: str) -> int:
         return int(N.lib().dg_segment_dim_cardinality(self.handle, dim.encode()))
 
