@@ -651,6 +651,75 @@ typedef struct {
 } dg_limit;
 
 int dg_result_limit(dg_result* res, const dg_limit* spec);
+/* ---- groupBy post-processing on the device ----
+ * GroupByQuery.postProcess over a resident dg_groupby_run* / dg_merge / dg_groupby_merge_devices result that
+ * has not been limited: the having spec (the HavingSpec classes of query/groupby/having), then DefaultLimitSpec.build
+ * (query/groupby/orderby/DefaultLimitSpec.java:122-290: makeComparator, metricOrdering, LimitingFn,
+ * TopNFunction; TopNSequence.java). One call applies, in this order:
+ *   1. having  keep the groups the postfix program accepts (n_having = 0: all of them)
+ *   2. order   sort = 1: the survivors by the comparator chain: bucket time first (last with
+ *              sort_by_dims_first on a non-ALL granularity, absent for ALL), the columns in their order.
+ *              Comparator-equal groups keep the result's key order (a stable sort; the reference's
+ *              MinMaxPriorityQueue leaves ties unspecified), or dimensions-then-time order with
+ *              sort_by_dims_first on a non-ALL granularity. sort = 0 (LimitingFn): the natural order.
+ *   3. limit   keep the first `limit` (0 = all)
+ * Afterwards the result holds exactly the surviving groups in that order, fetched as before, and counts as
+ * limited (dg_result_export refuses it, as does a second dg_result_post_process / dg_result_limit).
+ *
+ * The having program is postfix over a stack of booleans (at most DG_HAVING_MAX_OPS ops, at most 32
+ * operands alive). The device never parses numbers: every greaterThan / lessThan / equalTo leaf arrives as
+ * one closed interval of the aggregator's ORDER KEY, its own comparator as an unsigned 64-bit number
+ * (HavingSpecMetricComparator.java:36-80 is monotone in the metric for a fixed value):
+ *   long outputs    (Long.compare)     v ^ 2^63
+ *   double outputs  (Doubles.compare)  NaN -> ~0; else bits < 0 ? ~bits : bits | 2^63  (NaN greatest, -0.0 < 0.0)
+ *   float outputs                      the double key of the exactly widened float32
+ * An aggregator order column compares the same keys (AggregatorFactory.getComparator); a dimension column
+ * compares ranks (as dg_order_column) or ids when rank is NULL; a descending column is complemented.
+ *
+ * Refused before any launch, the result unchanged: an already limited result, a program that is too long
+ * or whose stack under- or overflows or does not end with one value, aggregator / dimension indices out of
+ * range, ranks outside [0, cardinality), a negative limit (DG_ERR_ARG); a result of 2^32 groups or more
+ * (DG_ERR_UNSUPPORTED: group references are 32-bit). On any later error the result is unchanged too. */
+#define DG_HAVING_MAX_OPS 128
+#define DG_HAVING_ALWAYS 0    /* push true */
+#define DG_HAVING_NEVER 1     /* push false */
+#define DG_HAVING_AND 2       /* pop `arg` operands, push their conjunction (arg = 0: true) */
+#define DG_HAVING_OR 3        /* pop `arg` operands, push their disjunction (arg = 0: false) */
+#define DG_HAVING_NOT 4       /* negate the top */
+#define DG_HAVING_AGG_RANGE 5 /* push lo <= order key of aggregator `arg` <= hi (lo > hi: never) */
+#define DG_HAVING_DIM_EQ 6    /* push (merged dictionary id of dimension `arg` == lo) */
+typedef struct {
+  int32_t op;  /* DG_HAVING_* */
+  int32_t arg;
+  uint64_t lo, hi;
+} dg_having_op;
+#define DG_ORDER_DIM 0
+#define DG_ORDER_AGG 1
+typedef struct {
+  int32_t kind;        /* DG_ORDER_DIM | DG_ORDER_AGG */
+  int32_t index;       /* into dg_groupby.dimensions / the call's aggregators */
+  int32_t descending;
+  int32_t reserved;
+  const int32_t* rank; /* DG_ORDER_DIM: as dg_order_column.rank; NULL = the id order */
+} dg_post_column;
+typedef struct {
+  const dg_having_op* having;
+  int32_t n_having;           /* 0 = no having spec */
+  int32_t n_columns;
+  const dg_post_column* columns;
+  int32_t sort;               /* 0 = LimitingFn: natural order, columns ignored after validation */
+  int32_t sort_by_dims_first; /* query context sortByDimsFirst */
+  int32_t limit;              /* 0 = none */
+  int32_t reserved;
+} dg_post_process;
+typedef struct {
+  int64_t groups_in;
+  int64_t groups_after_having;
+  int64_t groups_kept;
+  double having_ms; /* device time of the having pass and the survivor compaction (0 without phase timing) */
+  double sort_ms;   /* device time of the word loads, the sorts and the gather */
+} dg_post_info;
+int dg_result_post_process(dg_result* res, const dg_post_process* spec, dg_post_info* info /* may be NULL */);
 /* number of merged groups */
 int64_t dg_result_groups(const dg_result* res);
 /* groups [start, start + count), in result order (bucket time, then dimension values in Java

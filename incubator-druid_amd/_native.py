@@ -165,6 +165,35 @@ class dg_limit(ctypes.Structure):
                 ("sort_by_dims_first", ctypes.c_int32)]
 
 
+# dg_result_post_process: the having program's ops, the order columns, the spec and the out-struct
+HAVING_MAX_OPS = 128
+HAVING_ALWAYS, HAVING_NEVER, HAVING_AND, HAVING_OR, HAVING_NOT, HAVING_AGG_RANGE, HAVING_DIM_EQ = range(7)
+ORDER_DIM, ORDER_AGG = 0, 1
+
+
+class dg_having_op(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class dg_post_column(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32), ("descending", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("rank", ctypes.c_void_p)]
+
+
+class dg_post_process(ctypes.Structure):
+    _fields_ = [("having", ctypes.c_void_p), ("n_having", ctypes.c_int32), ("n_columns", ctypes.c_int32),
+                ("columns", ctypes.c_void_p), ("sort", ctypes.c_int32), ("sort_by_dims_first", ctypes.c_int32),
+                ("limit", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class dg_post_info(ctypes.Structure):
+    _fields_ = [("groups_in", ctypes.c_int64), ("groups_after_having", ctypes.c_int64),
+                ("groups_kept", ctypes.c_int64), ("having_ms", ctypes.c_double), ("sort_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class dg_keyspace(ctypes.Structure):
     _fields_ = [("n_dims", ctypes.c_int32), ("card", ctypes.c_void_p), ("period_ms", ctypes.c_int64),
                 ("bucket0", ctypes.c_int64), ("n_buckets", ctypes.c_int64), ("universal_time", ctypes.c_int64),
@@ -188,6 +217,7 @@ EXPORTS = [
     "dg_segment_num_dimensions", "dg_segment_dimension_name", "dg_debug_groupby_totals_source",
     "dg_groupby_run_dims", "dg_result_dim_type", "dg_result_dim_longs", "dg_debug_long_dim_info",
     "dg_topn_run_opts", "dg_topn_merge_opts", "dg_segment_numeric_dim_values", "dg_segment_numeric_dim_info",
+    "dg_result_post_process",
 ]
 
 _lib = None
@@ -256,6 +286,7 @@ def lib():
         "dg_result_dim_dictionary": (ctypes.c_int, [vp, i32, vp, vp, P(i64)]),
         "dg_result_release": (None, [vp]),
         "dg_result_limit": (ctypes.c_int, [vp, P(dg_limit)]),
+        "dg_result_post_process": (ctypes.c_int, [vp, P(dg_post_process), P(dg_post_info)]),
         "dg_keyspace_bits": (ctypes.c_int, [P(dg_keyspace), P(i32)]),
         "dg_result_export": (ctypes.c_int, [vp, P(dg_keyspace), P(vp), vp, vp]),
         "dg_keys_partition": (ctypes.c_int, [vp, vp, i64, vp, i32, vp]),

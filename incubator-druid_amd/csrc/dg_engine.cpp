@@ -5505,6 +5505,256 @@ int dg_result_limit(dg_result* r, const dg_limit* spec) {
   return DG_OK;
 }
 
+// GroupByQuery.postProcess on the device (the header's comment): having -> selection bitset -> ascending
+// survivor references (launch_rows_select); the comparator chain as sort words, least significant first,
+// each sorted by the stable unpacked radix sort (keys + u32 references) and the next one loaded through
+// the permuted references; launch_limit_gather of the first groups into new blocks. The survivor count is
+// known on the device only until the call's single read-back, so with a having spec the gather runs over
+// the host's bound (min(limit, n) groups) with the unused references zeroed, and the result's group count
+// is set from the read-back.
+int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_info* info) {
+  if (!r || !spec || spec->limit < 0 || spec->n_columns < 0 || (spec->n_columns > 0 && !spec->columns) ||
+      spec->n_having < 0 || (spec->n_having > 0 && !spec->having))
+    return set_error(DG_ERR_ARG, "bad post-processing spec");
+  if (r->limited) return set_error(DG_ERR_ARG, "the result is limited already (not in key order)");
+  if (spec->n_having > kPostMaxOps)
+    return set_error(DG_ERR_ARG, "having program of %d ops (max %d)", spec->n_having, kPostMaxOps);
+  if (r->ngroups >= (1ll << 32))
+    return set_error(DG_ERR_UNSUPPORTED, "%lld groups (group references are 32-bit)", (long long)r->ngroups);
+  if ((int)r->kinds.size() != r->naggs) return set_error(DG_ERR_ARG, "the result does not know its aggregators");
+  Context* ctx = r->ctx;
+  const KeyLayout& lay = r->lay;
+  // ---- the having program: indices and stack discipline ----
+  PostHaving hp;
+  memset(&hp, 0, sizeof hp);
+  hp.n = spec->n_having;
+  int depth = 0;
+  for (int i = 0; i < spec->n_having; ++i) {
+    const dg_having_op& h = spec->having[i];
+    hp.op[i] = h.op;
+    hp.lo[i] = h.lo;
+    hp.hi[i] = h.hi;
+    switch (h.op) {
+      case DG_HAVING_ALWAYS:
+      case DG_HAVING_NEVER: ++depth; break;
+      case DG_HAVING_AND:
+      case DG_HAVING_OR:
+        if (h.arg < 0 || h.arg > depth) return set_error(DG_ERR_ARG, "having op %d: %d operands of %d", i, h.arg, depth);
+        hp.arg[i] = h.arg;
+        depth += 1 - h.arg;
+        break;
+      case DG_HAVING_NOT:
+        if (depth < 1) return set_error(DG_ERR_ARG, "having op %d: NOT of an empty stack", i);
+        break;
+      case DG_HAVING_AGG_RANGE:
+        if (h.arg < 0 || h.arg >= r->naggs) return set_error(DG_ERR_ARG, "having op %d: aggregator %d of %d", i, h.arg, r->naggs);
+        hp.arg[i] = 1 + h.arg;
+        hp.kind[i] = r->kinds[h.arg];
+        ++depth;
+        break;
+      case DG_HAVING_DIM_EQ:
+        if (h.arg < 0 || h.arg >= r->ndims) return set_error(DG_ERR_ARG, "having op %d: dimension %d of %d", i, h.arg, r->ndims);
+        hp.arg[i] = lay.dim_shift[h.arg];
+        hp.kind[i] = lay.dim_bits[h.arg];
+        if (lay.dim_bits[h.arg] < 64 && (h.lo >> lay.dim_bits[h.arg])) {  // no id of the dimension: never
+          hp.op[i] = DG_HAVING_NEVER;
+        }
+        ++depth;
+        break;
+      default: return set_error(DG_ERR_ARG, "having op %d: unknown op %d", i, h.op);
+    }
+    if (depth > kPostMaxStack) return set_error(DG_ERR_ARG, "having op %d: more than %d operands alive", i, kPostMaxStack);
+  }
+  if (spec->n_having > 0 && depth != 1) return set_error(DG_ERR_ARG, "having program leaves %d values", depth);
+  // ---- the order columns ----
+  struct Field {
+    PostField f;
+    const int32_t* host_rank;
+    int32_t card;
+  };
+  std::vector<Field> chain;
+  auto key_field = [&](int d, int desc, const int32_t* rank) {  // d < 0: the bucket
+    Field x;
+    memset(&x, 0, sizeof x);
+    x.f.type = POST_F_KEY;
+    x.f.bits = d < 0 ? lay.bucket_bits : lay.dim_bits[d];
+    x.f.in_shift = d < 0 ? lay.bucket_shift : lay.dim_shift[d];
+    x.f.desc = desc;
+    x.host_rank = rank;
+    x.card = d < 0 ? 0 : dg_result_dim_cardinality(r, d);
+    if (x.f.bits > 0) chain.push_back(x);
+  };
+  const bool timed = lay.bucket_bits > 0;
+  const bool time_last = timed && spec->sort_by_dims_first != 0;
+  if (timed && !time_last) key_field(-1, 0, nullptr);
+  std::vector<bool> dim_used(r->ndims, false), agg_used(r->naggs, false);
+  for (int c = 0; c < spec->n_columns; ++c) {
+    const dg_post_column& oc = spec->columns[c];
+    if (oc.kind == DG_ORDER_DIM) {
+      if (oc.index < 0 || oc.index >= r->ndims) return set_error(DG_ERR_ARG, "ORDER BY dimension %d of %d", oc.index, r->ndims);
+      if (oc.rank) {
+        const int32_t card = dg_result_dim_cardinality(r, oc.index);
+        const int bits = lay.dim_bits[oc.index];
+        const int64_t top = bits >= 31 ? INT32_MAX : (1ll << bits);
+        for (int32_t i = 0; i < card; ++i)
+          if (oc.rank[i] < 0 || oc.rank[i] >= card || oc.rank[i] >= top)
+            return set_error(DG_ERR_ARG, "rank %d of id %d of dimension %d outside [0, %d)", oc.rank[i], i, oc.index, card);
+      }
+      if (dim_used[oc.index]) continue;  // a later mention never decides (the first already compared equal)
+      dim_used[oc.index] = true;
+      key_field(oc.index, oc.descending != 0, oc.rank);
+    } else if (oc.kind == DG_ORDER_AGG) {
+      if (oc.index < 0 || oc.index >= r->naggs) return set_error(DG_ERR_ARG, "ORDER BY aggregator %d of %d", oc.index, r->naggs);
+      if (agg_used[oc.index]) continue;
+      agg_used[oc.index] = true;
+      Field x;
+      memset(&x, 0, sizeof x);
+      const int k = r->kinds[oc.index];
+      const bool f32 = k == DG_AGG_FLOAT_SUM || k == DG_AGG_FLOAT_MIN || k == DG_AGG_FLOAT_MAX;
+      x.f.type = f32 ? POST_F_AGG32 : POST_F_AGG64;
+      x.f.bits = f32 ? 32 : 64;
+      x.f.desc = oc.descending != 0;
+      x.f.slot = 1 + oc.index;
+      x.f.kind = k;
+      chain.push_back(x);
+    } else {
+      return set_error(DG_ERR_ARG, "order column %d: unknown kind %d", c, oc.kind);
+    }
+  }
+  if (time_last) {
+    key_field(-1, 0, nullptr);
+    // comparator-equal groups in dimensions-then-time order (what the host's merge hands to its sort)
+    for (int d = 0; d < r->ndims; ++d) key_field(d, 0, nullptr);
+  }
+  const bool sort = spec->sort != 0 && !chain.empty();
+  const bool having = spec->n_having > 0;
+  const int64_t n = r->ngroups;
+  const int64_t m = spec->limit > 0 ? std::min<int64_t>(spec->limit, n) : n;  // groups kept at the most
+  dg_post_info pi;
+  memset(&pi, 0, sizeof pi);
+  pi.groups_in = pi.groups_after_having = n;
+  pi.groups_kept = m;
+  if (n == 0 || (!having && !sort)) {  // LimitingFn over the natural order: the first groups are the answer
+    r->ngroups = m;
+    r->limited = true;
+    if (info) *info = pi;
+    return DG_OK;
+  }
+  CallGuard g(ctx);
+  CallScratch* cs = g.cs;
+  hipStream_t st = ctx->stream;
+  // ---- words: the chain's fields packed most significant first; rank tables uploaded ----
+  std::vector<PostWord> words;
+  if (sort) {
+    for (Field& x : chain) {
+      if (x.host_rank) {
+        int32_t* dr;
+        int32_t* h = up_take<int32_t>(cs, (size_t)std::max(x.card, 1), &dr, st);
+        if (!h) return set_error(DG_ERR_OOM, "rank table");
+        memcpy(h, x.host_rank, sizeof(int32_t) * (size_t)x.card);
+        x.f.rank = dr;
+      }
+      if (words.empty() || words.back().bits + x.f.bits > 64 || words.back().nfields == kPostWordFields) {
+        PostWord w;
+        memset(&w, 0, sizeof w);
+        words.push_back(w);
+      }
+      PostWord& w = words.back();
+      w.f[w.nfields++] = x.f;
+      w.bits += x.f.bits;
+    }
+    for (PostWord& w : words) {
+      int out = w.bits;
+      for (int f = 0; f < w.nfields; ++f) {
+        out -= w.f[f].bits;
+        w.f[f].out_shift = out;
+      }
+    }
+  }
+  // ---- scratch, then the new blocks (before anything is launched or swapped) ----
+  SortBufs sb;
+  memset(&sb, 0, sizeof sb);
+  int rc = DG_OK;
+  if (sort) {
+    rc = sort_bufs(cs, n, 1, 64, 0, &sb, 32);  // (64 key bits + 32 reference bits: always keys + u32 references)
+    if (rc) return rc;
+  } else {
+    sb.cap = n;
+    sb.refs[0] = dev_take<uint32_t>(cs, (size_t)n + 16);
+    if (!sb.refs[0]) return set_error(DG_ERR_OOM, "survivor references of %lld groups", (long long)n);
+  }
+  uint32_t* sel = nullptr;
+  uint32_t* tile_cnt = nullptr;
+  unsigned long long *d_info = nullptr, *h_info = nullptr;
+  if (having) {
+    const int64_t nwords = (n + 31) / 32;
+    sel = dev_take<uint32_t>(cs, (size_t)nwords + 2);
+    tile_cnt = dev_take<uint32_t>(cs, (size_t)((nwords + kRowsTileWords - 1) / kRowsTileWords) + 1);
+    unsigned long long* z = up_take<unsigned long long>(cs, 4, &d_info, st);
+    h_info = host_take<unsigned long long>(cs, 4);
+    if (!sel || !tile_cnt || !z || !h_info) return set_error(DG_ERR_OOM, "having selection of %lld groups", (long long)n);
+    memset(z, 0, 32);
+  }
+  const int rec = r->naggs + 1;
+  DG_FLUSH(cs, st);
+  uint64_t* nk = static_cast<uint64_t*>(result_alloc(ctx, (size_t)std::max<int64_t>(m, 1) * 8));
+  uint64_t* ns = static_cast<uint64_t*>(result_alloc(ctx, (size_t)std::max<int64_t>(m, 1) * rec * 8));
+  auto drop = [&]() {
+    result_free(ctx, nk);
+    result_free(ctx, ns);
+  };
+  if (!nk || !ns) {
+    drop();
+    return set_error(DG_ERR_OOM, "post-processed result of %lld groups", (long long)m);
+  }
+  // ---- launches ----
+  phase_event(ctx->ev[0], st);
+  if (having) {
+    // references past the survivor count are never written: zeroed, so the gather's bound stays inside the result
+    for (int k = 0; k < 2; ++k)
+      if (sb.refs[k] && hipMemsetAsync(sb.refs[k], 0, ((size_t)n + 16) * 4, st) != hipSuccess) {
+        drop();
+        return set_error(DG_ERR_DEVICE, "hipMemsetAsync of the references");
+      }
+    launch_post_having(r->keys, r->slots, r->cap, n, hp, sel, st);
+    launch_rows_select(sel, n, (uint64_t)(sort ? n : m), tile_cnt, d_info, sb.refs[0], st);
+    cs->late.push_back({h_info, d_info, 32});
+  }
+  phase_event(ctx->ev[1], st);
+  for (int w = (int)words.size() - 1; w >= 0; --w) {  // LSD over the words
+    const bool first = w == (int)words.size() - 1;
+    const uint32_t* refs_in = first ? (having ? sb.refs[0] : nullptr) : sb.refs[sb.cur];
+    uint32_t* refs_out = first && !having ? sb.refs[sb.cur] : nullptr;  // (survivors already lie in refs[0] = refs[cur])
+    launch_post_sort_word(r->keys, r->slots, r->cap, n, d_info, refs_in, words[w], sb.keys[sb.cur], refs_out, sb.n, st);
+    launch_radix_sort(&sb, words[w].bits, st);
+  }
+  launch_limit_gather(&sb, m, r->keys, r->slots, r->cap, rec, nk, ns, std::max<int64_t>(m, 1), st);
+  phase_event(ctx->ev[2], st);
+  rc = finish_call(cs, st);
+  if (rc) {
+    drop();
+    return rc;
+  }
+  float hms = 0.f, sms = 0.f;
+  (void)phase_elapsed(&hms, ctx->ev[0], ctx->ev[1]);
+  (void)phase_elapsed(&sms, ctx->ev[1], ctx->ev[2]);
+  pi.having_ms = hms;
+  pi.sort_ms = sms;
+  if (having) {
+    pi.groups_after_having = (int64_t)h_info[0];
+    pi.groups_kept = std::min<int64_t>((int64_t)h_info[0], m);
+  }
+  result_free(ctx, r->keys);
+  result_free(ctx, r->slots);
+  r->keys = nk;
+  r->slots = ns;
+  r->cap = std::max<int64_t>(m, 1);
+  r->ngroups = pi.groups_kept;
+  r->limited = true;
+  if (info) *info = pi;
+  return DG_OK;
+}
+
 int32_t dg_result_dim_cardinality(const dg_result* r, int32_t dim) {
   if (!r || dim < 0 || dim >= r->ndims) return -1;
   if (r->dicts.empty()) return r->cards[dim];

@@ -1025,6 +1025,48 @@ void launch_limit_load(const uint64_t* keys, int64_t n, const LimitOrder& o, Sor
 // the first m elements of the sorted order: keys[ref] and the [rec][cap] slot-major records -> [rec][ocap]
 void launch_limit_gather(const SortBufs* sb, int64_t m, const uint64_t* keys, const uint64_t* slots, int64_t cap,
                          int rec, uint64_t* okeys, uint64_t* oslots, int64_t ocap, hipStream_t s);
+// dg_post.hip — groupBy post-processing on a resident result (dg_result_post_process): the having
+// tree as a postfix program over the groups' ABI-encoded slots and key fields, and the limit spec's
+// comparator chain as 64-bit sort words.
+constexpr int kPostMaxOps = DG_HAVING_MAX_OPS;
+constexpr int kPostMaxStack = 32;  // operands alive at once (a bit stack in one register pair)
+struct PostHaving {
+  int32_t n;
+  int32_t op[kPostMaxOps];    // DG_HAVING_*
+  int32_t arg[kPostMaxOps];   // AND / OR: operands; AGG_RANGE: slot row (1 + aggregator); DIM_EQ: the field's shift
+  int32_t kind[kPostMaxOps];  // AGG_RANGE: DG_AGG_*; DIM_EQ: the field's bits
+  uint64_t lo[kPostMaxOps];   // AGG_RANGE: the closed order-key interval; DIM_EQ: lo = the id
+  uint64_t hi[kPostMaxOps];
+};
+// sel[ceil(n / 32) + 2]: bit g = the program accepts group g (bits at or past n clear)
+void launch_post_having(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n, const PostHaving& p,
+                        uint32_t* sel, hipStream_t s);
+// One sort word: fields most significant first, each a key field (bucket / dimension id, through its
+// rank table if any), an aggregator's 64-bit order key or a float aggregator's 32-bit one;
+// a descending field is complemented within its bits.
+constexpr int kPostWordFields = 16;
+enum { POST_F_KEY = 0, POST_F_AGG64 = 1, POST_F_AGG32 = 2 };
+struct PostField {
+  int32_t type;      // POST_F_*
+  int32_t bits;
+  int32_t in_shift;  // key field: its shift inside the group's key
+  int32_t out_shift;
+  int32_t desc;
+  int32_t slot;      // aggregator field: slot row (1 + aggregator)
+  int32_t kind;      // aggregator field: DG_AGG_*
+  int32_t pad;
+  const int32_t* rank;
+};
+struct PostWord {
+  int32_t nfields;
+  int32_t bits;  // of the whole word (the sort's key_bits)
+  PostField f[kPostWordFields];
+};
+// kout[i] = word w of group g = refs_in ? refs_in[i] : i, for i < count (count = info ? info[1] : n);
+// refs_out (if given) [i] = g; n_out[0] = count
+void launch_post_sort_word(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n,
+                           const unsigned long long* info, const uint32_t* refs_in, const PostWord& w, uint64_t* kout,
+                           uint32_t* refs_out, uint32_t* n_out, hipStream_t s);
 // one record per run of the sorted merge input, partial values combined in order (device encoding,
 // SoA slots [rec][cap])
 void launch_merge_reduce(SortBufs* sb, const uint32_t* head_pos, const uint64_t* in_slots, AggPlan plan, int64_t cap,

@@ -83,6 +83,7 @@ class RunStats:
 
     def __init__(self):
         self.calls: List[Dict] = []
+        self.post: List[Dict] = []  # dg_post_info of every groupBy post-processing step on the device
 
     def add(self, m: N.dg_metrics, span=None):
         d = m.as_dict()
@@ -853,6 +854,7 @@ class GroupByResult:
         self.groups = int(N.lib().dg_result_groups(handle))
         self._dicts = dictionaries
         self.time_map: Optional[np.ndarray] = None  # bucket index -> time (a dg_merge over a calendar grid)
+        self.post_info: Optional[Dict] = None  # dg_post_info of apply_post_process, once it ran
 
     def dim_types(self, d: int) -> Tuple[int, int]:
         """(column type, output type) of dimension d as N.COL_* (dg_result_dim_type); a dg_merge result has
@@ -962,6 +964,76 @@ class GroupByResult:
         self.groups = int(N.lib().dg_result_groups(self.handle))
         return True
 
+    def post_process_spec(self):
+        """query.having / query.limitSpec as (having ops, order columns, sort, limit) of a
+        dg_result_post_process call, or None when there is nothing to apply or the spec cannot be
+        expressed: a having or an ORDER BY on a LONG-output dimension (postprocess_groupby refuses
+        those), an ORDER BY on an unknown column, a having leaf the program has no op for. Order columns
+        are (kind, index, descending, rank or None); dimension ranks are built as apply_limit_push_down
+        builds them."""
+        q = self.query
+        ls = q.limitSpec
+        if q.having is None and ls is None:
+            return None
+        ops: List = []
+        if q.having is not None:
+            try:
+                ops = having_program(q, self.dictionary)
+            except (ValueError, ArithmeticError):  # (a value the comparator itself refuses: the host path raises it)
+                return None
+            if ops is None:
+                return None
+        cols, sort, limit = [], False, 0
+        if ls is not None:
+            try:
+                sort = _limit_needs_sort(q)
+            except ValueError:
+                return None
+            aggs = {a.name: i for i, a in enumerate(q.aggregations)}
+            for c in ls.columns if sort else []:
+                if c.dimension in aggs:
+                    cols.append((N.ORDER_AGG, aggs[c.dimension], c.direction == "descending", None))
+                elif c.dimension in q.dimensions:
+                    d = q.dimensions.index(c.dimension)
+                    if q.dimensionTypes[d] != "STRING":
+                        return None
+                    rank = None
+                    if c.dimensionOrder != "lexicographic" or _beyond_bmp_low(self.dictionary(d)):
+                        rank = np.ascontiguousarray(O.DictionaryOrder(self.dictionary(d), c.dimensionOrder).rank,
+                                                    dtype=np.int32)
+                    cols.append((N.ORDER_DIM, d, c.direction == "descending", rank))
+                else:
+                    return None
+            if ls.limit is not None and ls.limit < (1 << 31):
+                limit = int(ls.limit)
+        return ops, cols, sort, limit
+
+    def apply_post_process(self) -> bool:
+        """GroupByQuery.postProcess on the device (dg_result_post_process): the having spec, then the
+        limit spec's order and cut, so that only the surviving groups are fetched. Returns whether the
+        device step ran (self.post_info then holds its dg_post_info); it does not when the query pushes
+        its limit down (apply_limit_push_down's case), has neither spec, or post_process_spec cannot
+        express it. The host's postprocess_groupby still runs over what is fetched: it is idempotent."""
+        q = self.query
+        if q.apply_limit_push_down():
+            return False
+        spec = self.post_process_spec()
+        if spec is None:
+            return False
+        ops, cols, sort, limit = spec
+        harr = (N.dg_having_op * max(len(ops), 1))(*[N.dg_having_op(*o) for o in ops])
+        carr = (N.dg_post_column * max(len(cols), 1))(
+            *[N.dg_post_column(k, i, int(desc), 0, rank.ctypes.data if rank is not None else None)
+              for k, i, desc, rank in cols])
+        pp = N.dg_post_process(ctypes.cast(harr, ctypes.c_void_p), len(ops), len(cols),
+                               ctypes.cast(carr, ctypes.c_void_p), int(sort),
+                               int(q._ctx_bool("sortByDimsFirst", False)), limit, 0)
+        info = N.dg_post_info()
+        N.check(N.lib().dg_result_post_process(self.handle, ctypes.byref(pp), ctypes.byref(info)))
+        self.post_info = info.as_dict()
+        self.groups = int(N.lib().dg_result_groups(self.handle))
+        return True
+
     def release(self):
         if self.handle:
             N.lib().dg_result_release(self.handle)
@@ -995,11 +1067,14 @@ def grouper_options(query: Q.GroupByQuery) -> Optional[Tuple[int, int]]:
 
 def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
                 stats: Optional[RunStats] = None, limit_push_down: bool = False,
-                cancel: Optional[ctypes.c_int32] = None) -> GroupByResult:
+                cancel: Optional[ctypes.c_int32] = None, post_process: bool = False) -> GroupByResult:
     """One dg_groupby_run over segments of ONE device: GroupByStrategyV2.mergeRunners over their
     per-segment runners (GroupByMergingQueryRunnerV2.java:170-290), the groups left in HBM. With
     `limit_push_down`, a query that pushes its limit down keeps only its first `limit` groups
     (GroupByResult.apply_limit_push_down); a result meant for the cross-device exchange stays whole.
+    With `post_process`, the having and limit specs are applied to the resident groups
+    (GroupByResult.apply_post_process): only for a result that holds every group of the query whole,
+    never for a partial that is merged with others afterwards.
     cancel: a flag another thread may set (Thread.interrupt): the call then fails DG_ERR_INTERRUPTED;
     the query context's "timeout" (ms) fails it with DG_ERR_TIMEOUT."""
     if len(_group_by_device(segments)) != 1:
@@ -1036,16 +1111,25 @@ def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     out = GroupByResult(res, query)
     if limit_push_down:
         out.apply_limit_push_down()
+    if post_process:
+        out.apply_post_process()
     return out
 
 
 def groupby_per_device(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
-                       stats: Optional[RunStats] = None) -> List[GroupByPartial]:
-    """The merged, ordered groups of every device's segments (one engine call per device)."""
+                       stats: Optional[RunStats] = None, post_process: bool = False) -> List[GroupByPartial]:
+    """The merged, ordered groups of every device's segments (one engine call per device).
+    post_process: the caller merges nothing else into these groups (the merged runner over one device's
+    segments), so the having and limit specs run on the device before the fetch; per-segment partials
+    and several devices' partials are merged first and stay whole."""
     out = []
-    for _, idx in _group_by_device(segments).items():
-        r = groupby_run([segments[i] for i in idx], query, stats, limit_push_down=True)
+    groups = _group_by_device(segments)
+    for _, idx in groups.items():
+        r = groupby_run([segments[i] for i in idx], query, stats, limit_push_down=True,
+                        post_process=post_process and len(groups) == 1)
         try:
+            if stats is not None and r.post_info is not None:
+                stats.post.append(r.post_info)
             out.append(r.fetch())
         finally:
             r.release()
@@ -1346,6 +1430,139 @@ def _limit_needs_sort(query: Q.GroupByQuery) -> bool:
 
 def _having_dimensions(h: Q.HavingSpec) -> List[str]:
     return ([h.dimension] if h.type == "dimSelector" else []) + [d for x in h.specs for d in _having_dimensions(x)]
+
+
+# ---- the same rules as a dg_result_post_process spec (the device step in front of the fetch) ----
+_KEY_MAX = (1 << 64) - 1
+_KEY_SIGN = 1 << 63
+_KEY_POS_INF = 0xFFF0000000000000  # order key of +inf: every key above it is NaN
+_KEY_NEG_INF = 0x000FFFFFFFFFFFFF  # order key of -inf
+
+
+def post_order_key(v, out_type: str) -> int:
+    """An aggregator's comparator as an unsigned 64-bit number (dg_result_post_process): Long.compare for
+    long outputs, Doubles.compare for double outputs (every NaN one key, the greatest; -0.0 < 0.0) and
+    for float outputs through their exactly widened value."""
+    if out_type == "long":
+        return (int(v) + _KEY_SIGN) & _KEY_MAX
+    d = float(v)
+    if d != d:
+        return _KEY_MAX
+    u = int(np.array([d], dtype=np.float64).view(np.uint64)[0])
+    return (~u & _KEY_MAX) if u & _KEY_SIGN else (u | _KEY_SIGN)
+
+
+def post_key_metric(key: int, out_type: str):
+    """The metric an order key stands for. No double has a key above +inf's but the NaN key, or below
+    -inf's: those read as NaN and as -inf, which keeps the comparator monotone over the whole key space."""
+    if out_type == "long":
+        return key - _KEY_SIGN
+    if key > _KEY_POS_INF:
+        return math.nan
+    if key < _KEY_NEG_INF:
+        return -math.inf
+    u = (key & ~_KEY_SIGN) if key & _KEY_SIGN else (~key & _KEY_MAX)
+    return float(np.array([u], dtype=np.uint64).view(np.float64)[0])
+
+
+def _key_compare(key: int, out_type: str, value) -> int:
+    """_having_compare of the key's metric. One corner is decided here: an infinite or NaN metric against
+    an integer value (a NumberFormatException of BigDecimal.valueOf in the reference) counts as below
+    every integer for -inf and above for +inf / NaN."""
+    metric = post_key_metric(key, out_type)
+    if out_type != "long" and isinstance(value, int) and (metric != metric or math.isinf(metric)):
+        return -1 if metric == -math.inf else 1
+    return _having_compare(metric, value)
+
+
+def having_interval(kind: str, out_type: str, value) -> Tuple[int, int]:
+    """The closed order-key interval [lo, hi] a greaterThan / lessThan / equalTo leaf accepts (lo > hi:
+    none): HavingSpecMetricComparator.compare is monotone in the metric for a fixed value, so the ends
+    are found by bisection over the key space with _having_compare itself."""
+    def first(pred):  # the least key with pred (monotone: false ... false true ... true), 2^64 when none
+        lo, hi = 0, _KEY_MAX + 1
+        while lo < hi:
+            mid = (lo + hi) >> 1
+            if pred(mid):
+                hi = mid
+            else:
+                lo = mid + 1
+        return lo
+
+    ge = first(lambda k: _key_compare(k, out_type, value) >= 0)
+    gt = first(lambda k: _key_compare(k, out_type, value) > 0)
+    lo, hi = {"greaterThan": (gt, _KEY_MAX), "lessThan": (0, ge - 1), "equalTo": (ge, gt - 1)}[kind]
+    return (lo, hi) if 0 <= lo <= hi <= _KEY_MAX else (1, 0)
+
+
+def having_program(query: Q.GroupByQuery, dictionary) -> Optional[List[Tuple[int, int, int, int]]]:
+    """query.having as dg_having_op tuples (op, arg, lo, hi) in postfix order, or None when it cannot be
+    expressed (a leaf on a LONG-output dimension, a metric leaf naming a dimension, a value that is no
+    number, a program beyond the ABI's length or stack). dictionary(d): the result's merged dictionary
+    of dimension d. A leaf on a name that is no aggregator folds to a constant, as _having_eval's
+    `metric is None` does; a dimSelector looks its value up (null and "" are the null id, an absent value
+    never matches)."""
+    aggs = {a.name: (i, a) for i, a in enumerate(query.aggregations)}
+    ops: List[Tuple[int, int, int, int]] = []
+
+    def const(b):
+        ops.append((N.HAVING_ALWAYS if b else N.HAVING_NEVER, 0, 0, 0))
+        return True
+
+    def emit(h: Q.HavingSpec) -> bool:
+        t = h.type
+        if t in ("always", "never"):
+            return const(t == "always")
+        if t in ("and", "or"):
+            if not all(emit(x) for x in h.specs):
+                return False
+            ops.append((N.HAVING_AND if t == "and" else N.HAVING_OR, len(h.specs), 0, 0))
+            return True
+        if t == "not":
+            if not emit(h.specs[0]):
+                return False
+            ops.append((N.HAVING_NOT, 0, 0, 0))
+            return True
+        if t == "dimSelector":
+            if h.dimension in aggs:
+                return False
+            if h.dimension not in query.dimensions:
+                return const((h.value or None) is None)
+            d = query.dimensions.index(h.dimension)
+            if query.dimensionTypes[d] != "STRING":
+                return False
+            want = h.value or None
+            if want is not None and not isinstance(want, str):
+                return False
+            ids = [i for i, v in enumerate(dictionary(d)) if (v or None) == want]
+            for i in ids:
+                ops.append((N.HAVING_DIM_EQ, d, i, 0))
+            if len(ids) != 1:
+                ops.append((N.HAVING_OR, len(ids), 0, 0))
+            return True
+        if t not in ("greaterThan", "lessThan", "equalTo"):
+            return False
+        if h.aggregation in query.dimensions:
+            return False
+        if h.aggregation not in aggs:  # metric is None
+            return const(_having_eval(h, Q.Row(0, {})))
+        if h.value is None:
+            return const(False)
+        if isinstance(h.value, bool) or not isinstance(h.value, (int, float)):
+            return False
+        i, a = aggs[h.aggregation]
+        lo, hi = having_interval(t, a.output_type, h.value)
+        ops.append((N.HAVING_AGG_RANGE, i, lo, hi))
+        return True
+
+    if not emit(query.having) or len(ops) > N.HAVING_MAX_OPS:
+        return None
+    depth = 0
+    for op, arg, _, _ in ops:  # the ABI's stack bound
+        depth += 1 - arg if op in (N.HAVING_AND, N.HAVING_OR) else (0 if op == N.HAVING_NOT else 1)
+        if depth > 32:
+            return None
+    return ops
 
 
 def postprocess_groupby(query: Q.GroupByQuery, rows: List[Q.Row]) -> List[Q.Row]:
@@ -1921,11 +2138,15 @@ class GroupByQueryRunnerFactory(TimeseriesQueryRunnerFactory):
         # the engine merges each device's segments (GroupByMergingQueryRunnerV2) and the devices'
         # results by value on the device (dg_groupby_merge_devices: peer copies, no host merge)
         if len(_group_by_device(segments)) == 1:
-            return self.toolchest.merge(query, groupby_per_device(segments, query, stats))
+            return self.toolchest.merge(query, groupby_per_device(segments, query, stats, post_process=True))
         res = groupby_merge_devices(segments, query, stats)
         try:
             for r in res:  # (each key range keeps its first `limit` groups; the toolchest re-limits)
                 r.apply_limit_push_down()
+                # a key range holds whole groups: having per range is exact, and the first `limit` of every
+                # range contain the first `limit` of them all
+                if r.apply_post_process() and stats is not None:
+                    stats.post.append(r.post_info)
             return self.toolchest.merge(query, [r.fetch() for r in res])
         finally:
             for r in res:
