@@ -868,7 +868,8 @@ int dg_debug_lz4_classify(const uint8_t* block, int32_t len, int32_t* kind);
  *   DG_PROBE_SORT      the groupBy sort alone: n packed [key | element index] words with the headline's key
  *                      shape (two uniform 17-bit dictionary ids below 100000), sorted by the engine's radix
  *                      passes (timed alone; the input is rewritten before each repetition) and checked
- *                      ascending afterwards (DG_ERR_DEVICE when not).
+ *                      ascending afterwards (DG_ERR_DEVICE when not). DG_PROBE_SORT_DEFER=d in the environment:
+ *                      only key bits [d, 34) are sorted and the check is on that prefix.
  *   DG_PROBE_CHAIN     n dependent one-workgroup kernels in a row on one stream (each reads the word its
  *                      predecessor wrote): the per-launch cost of a chain of small kernels
  *   DG_PROBE_CHAIN_GRAPH  the same chain captured once into a hipGraph and replayed with hipGraphLaunch
@@ -895,6 +896,13 @@ int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t iters, doubl
  * the histogram kernel over the call's elements (or no sort ran), 1 the segments' cached per-value row
  * counts (built by an earlier eligible groupBy over the same segments and last dimension). */
 int dg_debug_groupby_totals_source(dg_context* ctx, int32_t* source);
+
+/* The sort plan of the context's last groupBy call: out[0] = global radix passes of the plan (0: no sort
+ * ran), out[1] = low key bits left to the reduce (0: the classic sort over every key bit), out[2] = 1 when a
+ * run of equal sorted prefix was longer than the reduce orders and the call sorted classically after all
+ * (its result is the classic one). DG_GB_DEFER_BITS=k forces out[1] = k (0: classic), DG_GB_DEFER_PASSES=P the
+ * pass count, where the query allows a deferral at all. */
+int dg_debug_groupby_sort_plan(dg_context* ctx, int32_t out[3]);
 
 /* The cached long-dimension encoding of a LONG column (built by the first dg_groupby_run* that groups by
  * it or the first dg_topn_run_opts over it; no reference counterpart, the reference reads the long per row): *built = 0 / 1, *cardinality = its

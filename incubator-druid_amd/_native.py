@@ -215,6 +215,7 @@ EXPORTS = [
     "dg_groupby_run_opts", "dg_result_grouper_info", "dg_search_run",
     "dg_rows_run", "dg_rowset_rows", "dg_rowset_column_info", "dg_rowset_fetch", "dg_rowset_release",
     "dg_segment_num_dimensions", "dg_segment_dimension_name", "dg_debug_groupby_totals_source",
+    "dg_debug_groupby_sort_plan",
     "dg_groupby_run_dims", "dg_result_dim_type", "dg_result_dim_longs", "dg_debug_long_dim_info",
     "dg_topn_run_opts", "dg_topn_merge_opts", "dg_segment_numeric_dim_values", "dg_segment_numeric_dim_info",
     "dg_result_post_process",
@@ -302,6 +303,7 @@ def lib():
         "dg_debug_probe": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                           P(ctypes.c_double)]),
         "dg_debug_groupby_totals_source": (ctypes.c_int, [vp, P(i32)]),
+        "dg_debug_groupby_sort_plan": (ctypes.c_int, [vp, P(i32)]),
         "dg_groupby_run_dims": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_dimension), i32, P(dg_groupby_opts), P(vp),
                                                P(dg_metrics)]),
         "dg_result_dim_type": (ctypes.c_int, [vp, i32, P(i32), P(i32)]),

@@ -2317,9 +2317,10 @@ static bool has_float_sum(const AggPlan& plan) {
 // one_clear: the sort's and the reduce's control memory in the one-clear layout (SortBufs::ctl), for a
 // caller that issues launch_sort_ctl_clear once; otherwise every pass and the reduce clear their own
 static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bits, int pw, SortBufs* sb,
-                     int ref_bits = -1, bool one_clear = false) {
+                     int ref_bits = -1, bool one_clear = false, int defer_bits = 0) {
   memset(sb, 0, sizeof *sb);
   sb->cap = cap;
+  sb->defer_bits = defer_bits;  // (the passes and their control layout cover the key bits above them)
   sb->ntiles_sort = sort_tiles(cap);
   const int rb = ref_bits >= 0 ? ref_bits : bits_for(std::max<int64_t>(cap, 1));
   const bool packed = key_bits + rb <= 64;
@@ -2338,10 +2339,10 @@ static int sort_bufs(CallScratch* cs, int64_t cap, int ntiles_keygen, int key_bi
   sb->tile_cnt = dev_take<uint32_t>(cs, (size_t)std::max(ntiles_keygen, 1));
   sb->run_cnt = dev_take<uint32_t>(cs, (size_t)sb->ntiles_sort);
   if (one_clear) {
-    const size_t bytes = sort_ctl_bytes(sb, key_bits);
+    const size_t bytes = sort_ctl_bytes(sb, key_bits - defer_bits);
     uint8_t* ctl = dev_take<uint8_t>(cs, bytes);
     if (!sb->tile_cnt || !sb->run_cnt || !ctl) return set_error(DG_ERR_OOM, "sort tables");
-    sort_ctl_bind(sb, key_bits, ctl, bytes);
+    sort_ctl_bind(sb, key_bits - defer_bits, ctl, bytes);
     return DG_OK;
   }
   sb->n = dev_take<uint32_t>(cs, 4);
@@ -4688,6 +4689,7 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   CallGuard g(ctx);
   CallScratch* cs = g.cs;
   ctx->gb_totals_source = 0;
+  ctx->gb_sort_plan[0] = ctx->gb_sort_plan[1] = ctx->gb_sort_plan[2] = 0;
   Interrupt intr(q, t0);
   cs->intr = &intr;
   hipStream_t st = ctx->stream;
@@ -4765,10 +4767,62 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
     ntiles_rows += (int)((sv[i]->nrows + kTileRows - 1) / kTileRows);
   }
   if (row_total >= (1ll << 32)) return set_error(DG_ERR_UNSUPPORTED, "%lld rows in one call (row refs are 32-bit)", (long long)row_total);
+  // The sort plan (deferred low key bits): the global passes order key bits [d, key_bits) and
+  // the reduce orders each run of equal prefix in LDS. Allowed for the sort grouper over packed words
+  // without a floatSum (k_fsum_runs reads the globally sorted words); d = key_bits - 8 P for the fewest
+  // 8-bit passes P at which the expected elements per prefix, elements * 2^d / (buckets * the merged
+  // cardinalities), stay within 1 / kDeferPlanInvLambda — what the reduce orders for less than a pass
+  // costs, and far inside kDeferLambda, where a Poisson count passes kDeferMaxRun with probability
+  // below 1e-18. No P below the classic pass count, or a query shape that overflowed before: d = 0,
+  // today's sort. DG_GB_DEFER_BITS=k forces d = k (0: classic), DG_GB_DEFER_PASSES=P the
+  // pass count (same-box A/B and tests).
+  const GrouperChoice choice = resolve_grouper(opts, ctx->grouper, ctx->max_groups, getenv("DG_GROUPER"));
+  auto hash_runs = [&](int64_t elems) {
+    int64_t mg = std::max<int64_t>(elems, 1);
+    if (choice.max_groups > 0) mg = std::min(mg, choice.max_groups);
+    if (key_bits < 62) mg = std::min<int64_t>(mg, (int64_t)1 << key_bits);
+    return choice.grouper == DG_GROUPER_HASH && !has_float_sum(plan) && key_bits <= 63 && hash_capacity(mg) <= ((int64_t)1 << 31);
+  };
+  std::string shape;  // (segments, dimensions, granularity)
+  for (int i = 0; i < n; ++i) shape += std::to_string(sv[i]->uid) + ",";
+  for (int d = 0; d < nd; ++d) shape += std::string("|") + gb->dimensions[d];
+  shape += "|" + std::to_string(q->period_ms) + "|" + std::to_string(gr.nb);
+  auto plan_defer = [&](int64_t elems) {
+    const bool packed = key_bits + bits_for(std::max<int64_t>(elems, 1)) <= 64;
+    if (key_bits <= 1 || elems <= 0 || !packed || has_float_sum(plan) || hash_runs(elems)) return 0;
+    for (const std::string& s : ctx->gb_classic_shapes)  // (remembered overflows come before the switches)
+      if (s == shape) return 0;
+    const char* fb = getenv("DG_GB_DEFER_BITS");
+    if (fb && *fb) return std::min(std::max(atoi(fb), 0), key_bits - 1);
+    const int classic = radix_pass_count(key_bits);
+    const char* fp = getenv("DG_GB_DEFER_PASSES");
+    if (fp && *fp) {
+      const int p = atoi(fp);
+      return p >= 1 && p < classic ? std::max(key_bits - 8 * p, 0) : 0;
+    }
+    double space = lay.bucket_bits ? (double)std::max<int64_t>((gend - gb0) / q->period_ms, 1) : 1.0;
+    for (int d = 0; d < nd; ++d) space *= (double)std::max<int64_t>((int64_t)md[d]->card(), 1);
+    // (a first digit that leaves the last dimension's field brings k_rs_hist0 back in place of the value
+    // counts, about half a pass: such a plan has to save two passes, not one)
+    auto inside = [&](int d) {
+      const int w = radix_first_digit_bits(key_bits - d);
+      return nd > 0 && w > 0 && d + w <= lay.dim_bits[nd - 1];
+    };
+    for (int p = 1; p < classic; ++p) {
+      const int d = key_bits - 8 * p;
+      if (d <= 0) break;
+      if ((double)elems * std::ldexp(1.0, d) / space * kDeferPlanInvLambda > 1.0) continue;  // (<= kDeferLambda a fortiori)
+      if (inside(0) && !inside(d) && classic - p < 2) continue;
+      return d;
+    }
+    return 0;
+  };
+  int defer = 0;
   SortBufs sb;
   if (!any_multi) {
+    defer = plan_defer(row_total);
     // (the sort's control memory is cleared once, here, ahead of the decodes: launch_sort_ctl_clear)
-    rc = sort_bufs(cs, row_total, std::max(ntiles_rows, 1), key_bits, na, &sb, -1, true);
+    rc = sort_bufs(cs, row_total, std::max(ntiles_rows, 1), key_bits, na, &sb, -1, true, defer);
     if (rc) return rc;
     sb.row_refs = 1;
     launch_sort_ctl_clear(&sb, st);
@@ -4892,14 +4946,14 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   if (any_multi) {  // rows explode into one element per grouping: count them first to size the sort
     rc = count_elements(cs, d_jobs, d_tile, ntiles, &total, st);
     if (rc) return rc;
-    rc = sort_bufs(cs, total, ntiles, key_bits, na, &sb, -1, true);
+    defer = plan_defer(total);
+    rc = sort_bufs(cs, total, ntiles, key_bits, na, &sb, -1, true, defer);
     if (rc) return rc;
     launch_sort_ctl_clear(&sb, st);
   }
   // The grouper (dg_groupby_opts): the hash table is sized for max_groups = the limit, capped at the
   // call's elements and at the key space. Not eligible (the sort runs, same result): a floatSum plan
   // (k_fsum_runs walks sorted runs), a 64-bit key (~0 marks an empty position), positions beyond 32 bits.
-  const GrouperChoice choice = resolve_grouper(opts, ctx->grouper, ctx->max_groups, getenv("DG_GROUPER"));
   int64_t max_groups = std::max<int64_t>(total, 1);
   if (choice.max_groups > 0) max_groups = std::min(max_groups, choice.max_groups);
   if (key_bits < 62) max_groups = std::min<int64_t>(max_groups, (int64_t)1 << key_bits);
@@ -4947,8 +5001,9 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   CountTotals ctot{};
   std::vector<int> vc_build;  // segments whose last dimension's counts this call builds
   unsigned long long *d_vsum = nullptr, *h_vsum = nullptr;
-  const int fd_bits = radix_first_digit_bits(key_bits);
-  if (rows_elems && !use_hash && ntiles > 0 && total > 0 && nd > 0 && fd_bits > 0 && fd_bits <= lay.dim_bits[nd - 1] &&
+  // (the first digit: key bits [defer, defer + fd_bits))
+  const int fd_bits = radix_first_digit_bits(key_bits - defer);
+  if (rows_elems && !use_hash && ntiles > 0 && total > 0 && nd > 0 && fd_bits > 0 && defer + fd_bits <= lay.dim_bits[nd - 1] &&
       !env_on("DG_NO_COUNT_TOTALS")) {
     const int ld = nd - 1;
     bool ok = true;
@@ -5079,6 +5134,9 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   res->cap = cap;
   if (!res->keys || !res->slots) return set_error(DG_ERR_OOM, "groupBy result of %lld records", (long long)cap);
   bool reduce_timed = false;
+  int64_t* gb_carry_g = nullptr;  // the reduce's scratch (kept for a classic rerun)
+  int64_t* gb_open_g = nullptr;
+  uint64_t* gb_carry_slots = nullptr;
   if (use_hash) {
     const int64_t ngh = (int64_t)h_ctr[0];
     phase_event(ctx->ev[7], st);
@@ -5107,12 +5165,15 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
     if (side) DG_HIP(hipStreamWaitEvent(st, ctx->side_ev[2], 0));  // the payload is decoded
     phase_event(ctx->ev[7], st);
     reduce_timed = true;
+    gb_carry_g = carry_g;
+    gb_open_g = open_g;
+    gb_carry_slots = carry_slots;
     launch_gb_reduce(&sb, plan, res->keys, res->slots, cap, head_pos, carry_g, carry_slots, open_g, st);
     for (int a = 0; a < na; ++a)
       if (plan.kind[a] == DG_AGG_FLOAT_SUM) launch_fsum_runs(d_jobs, n, ntiles, &sb, plan, a, head_pos, res->slots, cap, st);
   }
   phase_event(ctx->ev[4], st);
-  if (!use_hash) DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));  // selected rows, groups
+  if (!use_hash) DG_HIP(hipMemcpyAsync(h_n, sb.n, 12, hipMemcpyDeviceToHost, st));  // selected rows, groups, run overflow
   if (!vc_build.empty()) DG_HIP(hipMemcpyAsync(h_vsum, d_vsum, 8 * vc_build.size(), hipMemcpyDeviceToHost, st));
   ht.mark("reduce_launched");
   rc = finish_call(cs, st);  // (polls the cancel flag / timeout while the device works)
@@ -5130,6 +5191,30 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
       c->vcnt_never = true;
       c->vcnt.reset();
     }
+  }
+  // A run of equal sorted prefix longer than the reduce orders (sb.n[2]): what it wrote is discarded. The
+  // ids and the payload are still decoded and the words are all there, ordered by their prefix with
+  // ties in element order, so the classic sort over every key bit starts from them (stable: the same
+  // order as from the unsorted words) and the reduce writes the same result buffers again. The shape is
+  // remembered: the next query like it sorts classically at once.
+  int reran = 0;
+  if (!use_hash && sb.defer_bits > 0 && h_n[2]) {
+    reran = 1;
+    sb.defer_bits = 0;
+    if (!sb.lb_status) sb.lb_status = dev_take<uint64_t>(cs, (size_t)kMaxBins * sb.ntiles_sort);
+    if (!sb.lb_status) return set_error(DG_ERR_OOM, "sort tables");
+    launch_radix_sort(&sb, key_bits, st);
+    launch_gb_reduce(&sb, plan, res->keys, res->slots, cap, nullptr, gb_carry_g, gb_carry_slots, gb_open_g, st);
+    DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    ctx->gb_classic_shapes.push_back(shape);
+    if (ctx->gb_classic_shapes.size() > 32) ctx->gb_classic_shapes.erase(ctx->gb_classic_shapes.begin());
+  }
+  if (!use_hash) {
+    ctx->gb_sort_plan[0] = radix_pass_count(key_bits - defer);
+    ctx->gb_sort_plan[1] = defer;
+    ctx->gb_sort_plan[2] = reran;
   }
   const int64_t nsel = h_n[0], ng = use_hash ? (int64_t)h_ctr[0] : (int64_t)h_n[1];
   // bufferGrouperMaxSize holds under either grouper (the hash grouper failed at its insert)
@@ -5188,7 +5273,9 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
     phase_elapsed(&fr, ctx->ev[7], ctx->ev[4]);
     m.reduce_kernel_ms = fr;
   }
-  m.sort_passes = key_bits > 0 ? (key_bits + 7) / 8 : 0;
+  // (the global passes that ran: the plan's, and the classic ones after an overflow)
+  m.sort_passes = use_hash ? (key_bits > 0 ? (key_bits + 7) / 8 : 0)
+                           : radix_pass_count(key_bits - defer) + (reran ? radix_pass_count(key_bits) : 0);
   m.key_bits = key_bits;
   m.groups = ng;
   m.total_ms = ms_since(t0);
@@ -6979,6 +7066,14 @@ extern "C" int dg_debug_probe(int32_t device, int32_t kind, int64_t n, int32_t i
   }
   hipStreamDestroy(st);
   return rc;
+}
+
+extern "C" int dg_debug_groupby_sort_plan(dg_context* c, int32_t out[3]) {
+  Context* ctx = reinterpret_cast<Context*>(c);
+  if (!ctx || !out) return set_error(DG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  for (int i = 0; i < 3; ++i) out[i] = ctx->gb_sort_plan[i];
+  return DG_OK;
 }
 
 extern "C" int dg_debug_groupby_totals_source(dg_context* c, int32_t* source) {

@@ -321,8 +321,12 @@ struct SortBufs {
   size_t ctl_bytes;
   uint64_t* pass_status[8];  // [kRsMaxPasses]
   uint64_t* red_status;
-  int ctl_key_bits;  // the sort the pass regions were laid out for
+  int ctl_key_bits;  // the sort the pass regions were laid out for: key bits [defer_bits, defer_bits + ctl_key_bits)
   int ctl_clean;
+  // Deferred low key bits (the groupBy sort plan): launch_radix_sort / launch_gb_sort_generated
+  // order the words by key bits [defer_bits, key_bits) only (ties in element order) and launch_gb_reduce
+  // finishes the order inside runs of equal prefix in LDS. 0: the classic sort over every key bit.
+  int defer_bits;
 };
 constexpr int kCtlSort = 1, kCtlReduce = 2;
 
@@ -555,6 +559,12 @@ struct Context {
   // the last groupBy call's source of its first sort pass's digit totals (dg_debug_groupby_totals_source):
   // 0 = k_rs_hist0 (or no sort), 1 = the segments' value counts
   int32_t gb_totals_source = 0;
+  // the last groupBy call's sort plan (dg_debug_groupby_sort_plan): global radix passes of the plan,
+  // deferred key bits, 1 when a run overflowed and the classic sort ran after it
+  int32_t gb_sort_plan[3] = {0, 0, 0};
+  // query shapes (segments, dimensions, granularity) whose deferred sort overflowed: they take the
+  // classic plan at once (most recent last, bounded like dict_cache)
+  std::vector<std::string> gb_classic_shapes;
   std::vector<std::shared_ptr<MergedDict>> dict_cache;  // most recent last
   // device blocks of groupBy results: live (size by pointer) and released for reuse
   std::map<void*, size_t> block_size;
@@ -637,7 +647,8 @@ void launch_probe_copy(const void* in, void* out, int64_t bytes, hipStream_t s);
 void launch_probe_chain(uint32_t* word, int n, hipStream_t s);
 void launch_probe_gather(const uint64_t* words, const void* rec, int64_t n, uint64_t* out, hipStream_t s);
 void launch_probe_fill(uint64_t* words, void* rec, int64_t n, hipStream_t s);
-// DG_PROBE_SORT: n words sorted iters times by launch_radix_sort (events around the sort only)
+// DG_PROBE_SORT: n words sorted iters times by launch_radix_sort (events around the sort only);
+// DG_PROBE_SORT_DEFER=d: key bits [d, 34) only, the check then on the sorted prefix
 int probe_sort(int64_t n, int iters, double* ms, hipStream_t st);
 void launch_mv_check(const MvCheck* d_jobs, int njobs, int32_t* d_err, hipStream_t s);
 // VSizeLongSerde.getSerializedSize (VSizeLongSerde.java:61-65)
@@ -841,6 +852,14 @@ constexpr int kTileRows = 2048;
 #endif
 constexpr int kMaxDigitBits = DG_RS_DIGIT_BITS;
 constexpr int kMaxBins = 1 << kMaxDigitBits;
+// longest run of equal sorted prefix the groupBy reduce orders in LDS (its halo on each side of a tile),
+// and the planner's bound on the expected elements per prefix
+constexpr int kDeferMaxRun = 64;
+constexpr int kDeferLambda = kDeferMaxRun / 4;
+// ... and on what the planner defers unasked: 1 / kDeferPlanInvLambda elements per prefix. The reduce pays
+// for every element inside a run (its walk, and a second payload gather for a displaced one): measured on
+// the headline, 0.04 per prefix leaves a gain of the pass saved, 0.64 none, 10 costs 2 ms.
+constexpr int kDeferPlanInvLambda = 8;
 constexpr int kRsMaxPasses = 8;  // 64 key bits at >= 8 bits per digit (rows of SortBufs::bin_total)
 constexpr int kSortTile = 4096;  // elements per radix / run tile (256 threads x 16)
 // groupBy reduce: waves per sort tile (each reduces its own 4096 / kRedWaves elements; one carry /
@@ -885,17 +904,18 @@ struct CountTotals {
   uint32_t n;     // elements of the call (stored to sb->n[0] by the totals kernel)
 };
 constexpr int32_t kErrDictId = 16;  // bit of the call's device error word: a dictionary id >= its cardinality
-// bits of the first digit of a sort over key_bits key bits (0: no pass)
+// bits of the first digit of a sort over key_bits key bits (0: no pass), and its passes
 int radix_first_digit_bits(int key_bits);
+int radix_pass_count(int key_bits);
 // counts[v] = rows of `ids` below nrows whose id is v (counts zeroed here); an id >= card is not counted
 // and raises kErrDictId; *sum = the counts' total (64-bit)
 void launch_value_counts(const ColView& ids, int64_t nrows, uint32_t card, uint32_t* counts, unsigned long long* sum,
                          int32_t* d_err, hipStream_t s);
-// stable LSD radix sort of sb->keys/refs[cur] on key bits [0, key_bits); ct: the first pass's digit
+// stable LSD radix sort of sb->keys/refs[cur] on key bits [sb->defer_bits, key_bits); ct: the first pass's digit
 // totals come from the value counts instead of k_rs_hist0
 void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s, const CountTotals* ct = nullptr);
 // The one-clear control layout of SortBufs (its comment): sort_ctl_bytes = the region's size for a sort
-// of key_bits key bits over sb->cap elements, sort_ctl_bind points n / bin_total / pass_status /
+// of key_bits key bits (those above sb->defer_bits) over sb->cap elements, sort_ctl_bind points n / bin_total / pass_status /
 // red_status into it (lb_status becomes null), launch_sort_ctl_clear zeroes it and marks it clean.
 size_t sort_ctl_bytes(const SortBufs* sb, int key_bits);
 void sort_ctl_bind(SortBufs* sb, int key_bits, void* mem, size_t bytes);
@@ -926,6 +946,9 @@ void launch_run_mark(SortBufs* sb, uint32_t* head_pos, hipStream_t s);
 // out_slots[s * cap + g] (SoA) in the ABI slot encoding; head_pos (null unless a floatSum needs it)
 // = first sorted element of run g; floatSum slots are left to launch_fsum_runs. carry_g / open_g:
 // sort_tiles(cap) entries, carry_slots: sort_tiles(cap) * (1 + naggs).
+// sb->defer_bits > 0 (packed words): each tile first orders the runs of equal sorted prefix it holds; a
+// run longer than kDeferMaxRun sets sb->n[2] and the result is then not to be used (the caller sorts
+// classically and reduces again).
 void launch_gb_reduce(SortBufs* sb, AggPlan plan, uint64_t* out_keys, uint64_t* out_slots, int64_t cap,
                       uint32_t* head_pos, int64_t* carry_g, uint64_t* carry_slots, int64_t* open_g, hipStream_t s);
 // floatSum aggregator `agg` as the reference computes it: a float32 sum in row order per run and

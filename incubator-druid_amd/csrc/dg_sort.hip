@@ -954,6 +954,13 @@ int radix_first_digit_bits(int key_bits) {
   return std::min(key_bits, w);
 }
 
+int radix_pass_count(int key_bits) {
+  if (key_bits <= 0) return 0;
+  int npass, w;
+  radix_digits(key_bits, &npass, &w);
+  return npass;
+}
+
 // 30-bit look-back counts hold every prefix (n <= cap); DG_SORT_WIDE_STATUS=1: 64-bit words regardless (tests)
 static bool rs_narrow_status(const SortBufs* sb) {
   const char* wide = getenv("DG_SORT_WIDE_STATUS");
@@ -1015,7 +1022,7 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGe
   const int nt = rs_scatter_tiles(sb);  // scatter tiles
   uint32_t* totals = sb->bin_total;                            // [npass][kMaxBins]
   uint32_t* ctr = sb->bin_total + kRsMaxPasses * kMaxBins;     // [npass] tile counters
-  const bool bound = sb->ctl && lo == 0 && hi == sb->ctl_key_bits;
+  const bool bound = sb->ctl && lo == sb->defer_bits && hi - lo == sb->ctl_key_bits;
   const bool clean = bound && (sb->ctl_clean & kCtlSort);
   sb->ctl_clean &= ~kCtlSort;
   if (!clean && !zero_async(sb->bin_total, ((size_t)kRsMaxPasses * kMaxBins + kRsMaxPasses) * sizeof(uint32_t), s)) return;
@@ -1068,12 +1075,12 @@ static void radix_passes(SortBufs* sb, int lo, int hi, hipStream_t s, const RsGe
 void launch_radix_sort(SortBufs* sb, int key_bits, hipStream_t s, const CountTotals* ct) {
   if (key_bits <= 0) return;
   static_assert(64 / kMaxDigitBits <= kRsMaxPasses, "passes of a 64-bit key");
-  radix_passes(sb, 0, key_bits, s, nullptr, ct);
+  radix_passes(sb, sb->defer_bits, key_bits, s, nullptr, ct);
 }
 
 bool radix_sort_generates(const SortBufs* sb, int key_bits, int64_t rows) {
   // (element indices are 32-bit: the last tile's indices past the rows must not wrap)
-  return key_bits > 0 && !sb->refs[0] && sb->row_refs && rows > 0 && rows <= (int64_t)0xFFFFFFFFll - kRsTile;
+  return key_bits > sb->defer_bits && !sb->refs[0] && sb->row_refs && rows > 0 && rows <= (int64_t)0xFFFFFFFFll - kRsTile;
 }
 
 void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, SortBufs* sb, int key_bits, hipStream_t s,
@@ -1086,7 +1093,7 @@ void launch_gb_sort_generated(const GbJob* d_jobs, int njobs, int64_t rows, Sort
     }
   }
   const RsGen gen{d_jobs, njobs, sb->ref_bits};
-  radix_passes(sb, 0, key_bits, s, &gen, ct);
+  radix_passes(sb, sb->defer_bits, key_bits, s, &gen, ct);
 }
 
 // DG_PROBE_SORT: the headline's sort words — [id0 (17 bits) | id1 (17 bits) | element index], the ids
@@ -1101,9 +1108,10 @@ __global__ void k_probe_sort_fill(uint64_t* __restrict__ keys, int64_t n, int re
     keys[i] = (key << ref_bits) | (uint64_t)i;
   }
 }
-__global__ void k_probe_sort_check(const uint64_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ bad) {
+// (shift > 0: only the bits from there up were sorted — equal prefixes may follow one another)
+__global__ void k_probe_sort_check(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ bad) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i + 1 < n; i += (int64_t)gridDim.x * blockDim.x)
-    if (keys[i] >= keys[i + 1]) atomicAdd(bad, 1u);
+    if (shift ? (keys[i] >> shift) > (keys[i + 1] >> shift) : keys[i] >= keys[i + 1]) atomicAdd(bad, 1u);
 }
 
 int probe_sort(int64_t n, int iters, double* ms, hipStream_t st) {
@@ -1116,6 +1124,8 @@ int probe_sort(int64_t n, int iters, double* ms, hipStream_t st) {
   while ((1ll << rb) < n) ++rb;
   sb.ref_bits = rb;
   const int key_bits = 34;
+  const char* dv = getenv("DG_PROBE_SORT_DEFER");
+  sb.defer_bits = dv ? std::min(std::max(atoi(dv), 0), key_bits - 1) : 0;
   void* mem[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const size_t sz[5] = {((size_t)n + 16) * 8, ((size_t)n + 16) * 8, (size_t)kMaxBins * sb.ntiles_sort * 8,
                         ((size_t)kMaxBins * kRsMaxPasses + kRsMaxPasses + 1) * 4, 16};
@@ -1141,7 +1151,8 @@ int probe_sort(int64_t n, int iters, double* ms, hipStream_t st) {
       launch_radix_sort(&sb, key_bits, st);
       (void)hipEventRecord(e1, st);
       (void)hipMemsetAsync(sb.n + 1, 0, 4, st);
-      hipLaunchKernelGGL(k_probe_sort_check, dim3(4096), dim3(256), 0, st, sb.keys[sb.cur], n, sb.n + 1);
+      hipLaunchKernelGGL(k_probe_sort_check, dim3(4096), dim3(256), 0, st, sb.keys[sb.cur], n,
+                         sb.defer_bits ? rb + sb.defer_bits : 0, sb.n + 1);
       uint32_t bad = 0;
       (void)hipMemcpyAsync(&bad, sb.n + 1, 4, hipMemcpyDeviceToHost, st);
       if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
@@ -1252,10 +1263,18 @@ constexpr int kRSPT = kSortTile / kRT;          // elements per lane
 // __syncthreads would wait for them: s_waitcnt vmcnt(0) before s_barrier; measured equal or slower).
 __device__ __forceinline__ void red_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <bool REFS>
+// DEFER (packed words only): the sort ordered the words by word >> (kshift + dbits) alone, ties in
+// element order. The tile loads its full words and kDeferMaxRun more on each side, every element of a
+// run of equal prefix takes the position run start + (words of the run smaller than its own) — words
+// are unique (they hold the row ref), so that is the order of the sort over every key bit — and the
+// window is rewritten in LDS before anything else looks at it. A run of at most kDeferMaxRun elements
+// that holds an element of the tile lies wholly inside the window, so neighbouring tiles order a shared
+// run alike. A longer one sets n_ptr[2]; the tile goes on as ever (every position stays inside the
+// window, every stored word is one it loaded) and the caller discards the result.
+template <bool REFS, bool DEFER>
 __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __restrict__ payload, int pw,
                                                    const uint64_t* __restrict__ keys, const uint32_t* __restrict__ refs,
-                                                   int kshift, uint32_t* __restrict__ n_ptr,
+                                                   int kshift, int dbits, uint32_t* __restrict__ n_ptr,
                                                    uint64_t* __restrict__ status, uint32_t* __restrict__ tile_ctr,
                                                    AggPlan plan,
                                                    uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_slots,
@@ -1271,8 +1290,13 @@ __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __r
   // counts (tiles take their index from a counter as they start, so a tile only waits on running
   // ones); the last tile publishes the group count (n_ptr[1]). No separate run-count pass over the
   // keys, no host read-back before the reduce: the result is laid out for `cap` (>= groups) records.
+  static_assert(!DEFER || !REFS, "deferred key bits are finished on packed words");
   constexpr int kWSeg = kSortTile / kRedWaves;
-  __shared__ uint64_t s_key[kSortTile + 2];  // [0] = element before the tile, [1 + x] = element x
+  constexpr int kH = kDeferMaxRun;  // DEFER: window position of element x = kH + x
+  static_assert(2 * kH <= kRT, "one thread per halo word");
+  // [0] = element before the tile, [1 + x] = element x (DEFER: the window's full words; key_at)
+  __shared__ uint64_t s_key[DEFER ? kSortTile + 2 * kH : kSortTile + 2];
+  auto key_at = [&](int i) -> uint64_t { return DEFER ? s_key[kH - 1 + i] >> kshift : s_key[i]; };
   __shared__ uint32_t s_heads[kRedWaves];
   __shared__ int s_tile;
   __shared__ int64_t s_gbase;
@@ -1299,36 +1323,124 @@ __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __r
     kw[c] = x < tile_n ? keys[base + x] : 0ull;
     idx_of[c] = REFS ? (x < tile_n ? refs[base + x] : 0u) : 0u;
   }
-#pragma unroll
-  for (int c = 0; c < kRSPT; ++c) {
-    const int x = wbase + c * 64 + lane;
-    s_key[1 + x] = kw[c] >> kshift;
-    if (!REFS) idx_of[c] = (uint32_t)(kw[c] & kmask);
-  }
   const bool has_next = base + kSortTile < n;
-  if (tid == 0) {
-    s_key[0] = base > 0 ? keys[base - 1] >> kshift : ~(keys[0] >> kshift);
-    if (has_next) s_key[1 + kSortTile] = keys[base + kSortTile] >> kshift;
-  }
   // up to two payload slots per element, gathered once and together (random record reads in flight)
   constexpr int kRegSlots = 2;
   uint64_t xr[kRSPT][kRegSlots];
-  if (pw <= kRegSlots) {
+  auto gather = [&](int c, uint64_t* dst) {
+    const bool valid = wbase + c * 64 + lane < tile_n;
+    const uint64_t* pr = payload + (size_t)idx_of[c] * pw;
+    if (pw == 2 && valid) {
+      const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(pr);  // 16-byte aligned: pw == 2
+      dst[0] = w.x;
+      dst[1] = w.y;
+    } else {
+      dst[0] = valid && pw >= 1 ? pr[0] : 0ull;
+      dst[1] = 0ull;
+    }
+  };
+  // DEFER: elements whose place another element took, and that element's payload (gathered late)
+  uint32_t moved = 0;
+  uint64_t xm[DEFER ? kRSPT : 1][kRegSlots];
+  if (DEFER) {
+    // the window's valid positions [jlo, jhi): the halo is clamped at the array's ends
+    const int jlo = base >= kH ? 0 : (int)(kH - base);
+    const int jhi = (int)min<int64_t>(kSortTile + 2 * kH, (int64_t)n - base + kH);
+    const int ps = kshift + dbits;
+    constexpr int kE = kRSPT + 1;  // my tile elements and, in the first 2 kH threads, one halo word
+    int jj[kE], ja[kE], jb[kE], cn[kE];
+    uint64_t ww[kE];
+    uint32_t actl = 0, actr = 0;  // elements still walking to their run's start / end
+    jj[kRSPT] = tid < kH ? tid : kSortTile + tid;
+    ww[kRSPT] = 0ull;
+    const bool halo = tid < 2 * kH && jj[kRSPT] >= jlo && jj[kRSPT] < jhi;
+    if (halo) ww[kRSPT] = keys[base - kH + jj[kRSPT]];
+    // The payload of the elements as loaded, gathered at once as the classic reduce does (the random
+    // reads are in flight while the runs are ordered): at one group per row nearly every element
+    // keeps its place. A position another element moves into gathers that one's record afterwards.
+#pragma unroll
+    for (int c = 0; c < kRSPT; ++c) idx_of[c] = (uint32_t)(kw[c] & kmask);
+    if (pw <= kRegSlots) {
+#pragma unroll
+      for (int c = 0; c < kRSPT; ++c) gather(c, xr[c]);
+    }
 #pragma unroll
     for (int c = 0; c < kRSPT; ++c) {
-      const bool valid = wbase + c * 64 + lane < tile_n;
-      const uint64_t* pr = payload + (size_t)idx_of[c] * pw;
-      if (pw == 2 && valid) {
-        const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(pr);  // 16-byte aligned: pw == 2
-        xr[c][0] = w.x;
-        xr[c][1] = w.y;
-      } else {
-        xr[c][0] = valid && pw >= 1 ? pr[0] : 0ull;
-        xr[c][1] = 0ull;
+      const int x = wbase + c * 64 + lane;
+      jj[c] = kH + x;
+      ww[c] = kw[c];
+      s_key[kH + x] = kw[c];
+      if (x < tile_n) actl |= 1u << c;
+    }
+    if (tid < 2 * kH) s_key[jj[kRSPT]] = ww[kRSPT];
+    if (halo) actl |= 1u << kRSPT;
+    actr = actl;
+    const uint32_t mine = actl;
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+      ja[e] = jb[e] = jj[e];
+      cn[e] = 0;
+    }
+    red_barrier();  // the window's words are in LDS
+    // (an element whose prefix differs from both neighbours leaves after one step: the headline's common case)
+    for (int s = 0; s < kH && (actl | actr); ++s) {
+#pragma unroll
+      for (int e = 0; e < kE; ++e) {
+        if ((actl >> e) & 1u) {
+          const uint64_t y = ja[e] > jlo ? s_key[ja[e] - 1] : 0ull;
+          if (ja[e] > jlo && (y >> ps) == (ww[e] >> ps)) {
+            cn[e] += y < ww[e] ? 1 : 0;
+            --ja[e];
+          } else {
+            actl &= ~(1u << e);
+          }
+        }
+        if ((actr >> e) & 1u) {
+          const uint64_t y = jb[e] + 1 < jhi ? s_key[jb[e] + 1] : 0ull;
+          if (jb[e] + 1 < jhi && (y >> ps) == (ww[e] >> ps)) {
+            cn[e] += y < ww[e] ? 1 : 0;
+            ++jb[e];
+          } else {
+            actr &= ~(1u << e);
+          }
+        }
       }
     }
+    bool over = false;
+#pragma unroll
+    for (int c = 0; c < kRSPT; ++c) over |= ((mine >> c) & 1u) && jb[c] - ja[c] + 1 > kH;
+    if (over) n_ptr[2] = 1u;  // (nothing waits on it: the call's end reads it)
+    red_barrier();  // every walk has read the window
+#pragma unroll
+    for (int e = 0; e < kE; ++e)
+      if (((mine >> e) & 1u) && ja[e] + cn[e] != jj[e]) s_key[ja[e] + cn[e]] = ww[e];
+    red_barrier();  // the window is in the order of the sort over every key bit
+#pragma unroll
+    for (int c = 0; c < kRSPT; ++c) {
+      kw[c] = s_key[kH + wbase + c * 64 + lane];
+      if (((mine >> c) & 1u) && kw[c] != ww[c]) {
+        moved |= 1u << c;
+        idx_of[c] = (uint32_t)(kw[c] & kmask);
+        if (pw <= kRegSlots) gather(c, xm[c]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < kRSPT; ++c) {
+      const int x = wbase + c * 64 + lane;
+      s_key[1 + x] = kw[c] >> kshift;
+      if (!REFS) idx_of[c] = (uint32_t)(kw[c] & kmask);
+    }
+    if (tid == 0) {
+      s_key[0] = base > 0 ? keys[base - 1] >> kshift : ~(keys[0] >> kshift);
+      if (has_next) s_key[1 + kSortTile] = keys[base + kSortTile] >> kshift;
+    }
   }
-  red_barrier();  // the tile's keys are in LDS (the payload gathers stay in flight)
+  if (!DEFER && pw <= kRegSlots) {
+#pragma unroll
+    for (int c = 0; c < kRSPT; ++c) gather(c, xr[c]);
+  }
+  if (!DEFER) red_barrier();  // the tile's keys are in LDS (the payload gathers stay in flight)
   // run heads / ends of my elements, and the groups whose head lies before my share
   uint32_t hm = 0, tm = 0;
   uint32_t nh = 0;  // heads in my share
@@ -1336,10 +1448,11 @@ __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __r
   for (int c = 0; c < kRSPT; ++c) {
     const int x = wbase + c * 64 + lane;
     const bool valid = x < tile_n;
-    const uint64_t k = s_key[1 + x];
-    const bool h = valid && k != s_key[x];
+    const uint64_t k = key_at(1 + x);
+    // (DEFER: no word lies before the first tile, where the classic layout keeps a sentinel)
+    const bool h = valid && (k != key_at(x) || (DEFER && base + x == 0));
     bool t = false;
-    if (valid) t = x + 1 < tile_n ? s_key[2 + x] != k : (!has_next || s_key[1 + kSortTile] != k);
+    if (valid) t = x + 1 < tile_n ? key_at(2 + x) != k : (!has_next || key_at(1 + kSortTile) != k);
     hm |= (uint32_t)h << c;
     tm |= (uint32_t)t << c;
     nh += (uint32_t)__popcll(__ballot(h));
@@ -1396,7 +1509,7 @@ __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __r
       heads += __popcll(bal);
       if (h) {
         const int x = wbase + c * 64 + lane;
-        out_keys[Gq + grel[c]] = s_key[1 + x];
+        out_keys[Gq + grel[c]] = key_at(1 + x);
         if (head_pos) head_pos[Gq + grel[c]] = (uint32_t)(base + x);
       }
     }
@@ -1416,6 +1529,7 @@ __global__ __launch_bounds__(kRT, kRedMinW) void k_gb_reduce(const uint64_t* __r
       uint64_t xv;
       if (!valid) xv = ident;
       else if (a < 0) xv = 1ull;
+      else if (pw <= kRegSlots && DEFER && ((moved >> c) & 1u)) xv = a == 0 ? xm[c][0] : xm[c][1];
       else if (pw <= kRegSlots) xv = a == 0 ? xr[c][0] : xr[c][1];
       else xv = payload[pay_at(pw, idx_of[c], a)];
       uint64_t v = xv;
@@ -1499,13 +1613,18 @@ void launch_gb_reduce(SortBufs* sb, AggPlan plan, uint64_t* out_keys, uint64_t* 
     if (!zero_async(ctr, sizeof(uint32_t), s)) return;
     if (!zero_async(sb->n + 1, sizeof(uint32_t), s)) return;
   }
+  if (!clean && sb->defer_bits && !zero_async(sb->n + 2, sizeof(uint32_t), s)) return;  // (the overflow flag)
   if (refs)
-    hipLaunchKernelGGL(k_gb_reduce<true>, dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
-                       sb->ref_bits, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
+    hipLaunchKernelGGL((k_gb_reduce<true, false>), dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
+                       sb->ref_bits, 0, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
+                       carry_g, carry_slots, open_g);
+  else if (sb->defer_bits)
+    hipLaunchKernelGGL((k_gb_reduce<false, true>), dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
+                       sb->ref_bits, sb->defer_bits, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
                        carry_g, carry_slots, open_g);
   else
-    hipLaunchKernelGGL(k_gb_reduce<false>, dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
-                       sb->ref_bits, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
+    hipLaunchKernelGGL((k_gb_reduce<false, false>), dim3(nt), dim3(kRT), 0, s, sb->payload, sb->pw, sb->keys[sb->cur], refs,
+                       sb->ref_bits, 0, sb->n, status, ctr, plan, out_keys, out_slots, cap, head_pos,
                        carry_g, carry_slots, open_g);
   const int64_t nw = (int64_t)nt * kRedWaves;  // carry / open slots: one per wave share of a tile
   const unsigned g = (unsigned)((nw + 255) / 256);
