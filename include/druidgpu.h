@@ -108,6 +108,35 @@ extern "C" {
 #define DG_AGG_DOUBLE_MAX 7
 #define DG_AGG_FLOAT_MIN 8
 #define DG_AGG_FLOAT_MAX 9
+/* First / last aggregators (query/aggregation/first/{Long,Double,Float}FirstAggregatorFactory.java,
+ * query/aggregation/last/{Long,Double,Float}LastAggregatorFactory.java): the value at the earliest /
+ * latest __time of the cell's rows. The reference's buffer is a 16-byte (time, value) pair
+ * (SerializablePair<Long, ...>): first/LongFirstBufferAggregator.java:48-56 updates it when
+ * time < firstTime (init (Long.MAX_VALUE, 0): of the rows sharing the smallest time the one the cursor
+ * reaches first wins), last/LongLastBufferAggregator.java:50-56 when time >= lastTime (init
+ * (Long.MIN_VALUE, 0): of the rows sharing the largest time the one the cursor reaches last wins); a
+ * descending scan (dg_scan.descending, timeseries and topN) reverses the cursor. Here the pair is two
+ * aggregator entries: the first/last entry's slot holds the pair's value (rhs: int64, double, or float32 in
+ * the low 4 bytes; an empty cell holds 0) and the entry directly after it MUST be DG_AGG_PAIR_TIME, whose
+ * int64 slot holds the pair's time (lhs: the smallest / largest __time of the cell's rows; an empty cell
+ * holds Long.MAX_VALUE / Long.MIN_VALUE). The DG_AGG_PAIR_TIME entry has a NULL field and no filter of
+ * its own: it inherits its pair's (a FilteredAggregatorFactory wraps the whole pair). A DG_AGG_PAIR_TIME
+ * anywhere else, or a first/last entry without it, is DG_ERR_ARG. A pair therefore costs two of the 16
+ * aggregator entries of a call. dg_records_pack lays the reference's 16-byte [time][value] record out with
+ * the two entries' offsets. Merges combine a pair by the factories' rule
+ * (LongFirstAggregatorFactory.java:103-112: lhs.time <= rhs.time ? lhs : rhs;
+ * LongLastAggregatorFactory.java:107: lhs.time > rhs.time ? lhs : rhs) and order by the value
+ * (getComparator: Longs / Doubles / Floats.compare of rhs). A call whose times and rows do not fit the
+ * engine's 63-bit (time, cursor position) key — bits(max time - min time) + bits(rows - 1) > 63 — is
+ * DG_ERR_UNSUPPORTED, as are the device-side groupBy merges (dg_keyspace_bits, dg_result_export, dg_merge,
+ * dg_groupby_merge_devices) of these kinds. */
+#define DG_AGG_LONG_FIRST 10
+#define DG_AGG_LONG_LAST 11
+#define DG_AGG_DOUBLE_FIRST 12
+#define DG_AGG_DOUBLE_LAST 13
+#define DG_AGG_FLOAT_FIRST 14
+#define DG_AGG_FLOAT_LAST 15
+#define DG_AGG_PAIR_TIME 16
 
 /* filter node kinds (query/filter/...DimFilter.java -> segment/filter/...Filter.java) */
 #define DG_F_AND 1

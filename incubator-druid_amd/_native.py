@@ -456,8 +456,10 @@ def make_scan(query, query_module, cancel: Optional[ctypes.c_int32] = None, segm
     keep = []
     fp = FilterProgram(query.effective_filter() if filters else None, query_module, segments)
     keep.append(fp)
-    aggs = (dg_agg * max(len(query.aggregations), 1))()
-    for i, a in enumerate(query.aggregations):
+    # (a first/last aggregator is followed by its DG_AGG_PAIR_TIME entry: no field, no filter of its own)
+    native_aggs = query_module.native_aggregations(query.aggregations)
+    aggs = (dg_agg * max(len(native_aggs), 1))()
+    for i, a in enumerate(native_aggs):
         aggs[i].kind = a.kind
         fld = _b(a.fieldName) if a.kind != 0 else None
         keep.append(fld)
@@ -492,7 +494,7 @@ def make_scan(query, query_module, cancel: Optional[ctypes.c_int32] = None, segm
         s.filter = ctypes.cast(fp.array, ctypes.POINTER(dg_filter))
         s.n_filter = len(fp.nodes)
     s.aggs = ctypes.cast(aggs, ctypes.POINTER(dg_agg))
-    s.n_aggs = len(query.aggregations)
+    s.n_aggs = len(native_aggs)
     if cancel is not None:
         s.cancel = ctypes.pointer(cancel)
         keep.append(cancel)

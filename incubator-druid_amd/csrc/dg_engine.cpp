@@ -1700,16 +1700,124 @@ static uint64_t finalize_slot(int kind, uint64_t s) {
   }
 }
 
-static int make_plan(const dg_scan* q, AggPlan* plan) {
+// First / last aggregators (DG_AGG_*_FIRST / *_LAST + DG_AGG_PAIR_TIME, dg_firstlast.hip). The engines
+// aggregate them as internal slots: a first/last entry is a longMin (first) / longMax (last) over the
+// segment's synthesized (time, cursor position) key column, its DG_AGG_PAIR_TIME a longMin / longMax over
+// __time under the pair's filter. FlPlan keeps what the AggPlan of those internal kinds does not say:
+// the engine's aggregator list (aggs, what the engines read in place of dg_scan.aggs), the value column
+// of each first/last slot, and per slot the output-side kind — after k_fl_resolve a first/last slot
+// holds its pair's value in the slot encoding of a sum of that type, so finalize_slot, the topN metric
+// keys and the groupBy result's post-processing treat it as DG_AGG_LONG_SUM / DOUBLE_SUM / FLOAT_SUM.
+struct FlPlan {
+  bool any = false;
+  int32_t okind[kMaxAggs];      // output-side kind of every slot (the plan's kind for the other aggregators)
+  int32_t abi_kind[kMaxAggs];   // the caller's DG_AGG_*
+  const char* field[kMaxAggs];  // first/last slot: its value column
+  dg_agg aggs[kMaxAggs];
+};
+static bool is_first_last(int k) { return k >= DG_AGG_LONG_FIRST && k <= DG_AGG_FLOAT_LAST; }
+static bool fl_first(int k) { return ((k - DG_AGG_LONG_FIRST) & 1) == 0; }
+static int fl_value_kind(int k) {
+  return k <= DG_AGG_LONG_LAST ? DG_AGG_LONG_SUM : k <= DG_AGG_DOUBLE_LAST ? DG_AGG_DOUBLE_SUM : DG_AGG_FLOAT_SUM;
+}
+static const char* agg_kind_name(int k) {
+  static const char* const names[] = {"count",     "longSum",  "doubleSum", "floatSum",   "longMin",    "longMax",
+                                      "doubleMin", "doubleMax", "floatMin",  "floatMax",   "longFirst",  "longLast",
+                                      "doubleFirst", "doubleLast", "floatFirst", "floatLast", "the time of a first/last pair"};
+  return k >= 0 && k <= DG_AGG_PAIR_TIME ? names[k] : "?";
+}
+// the first first/last (or pair-time) kind among n kinds, or -1
+static int find_first_last(const int32_t* kinds, int n) {
+  for (int a = 0; a < n; ++a)
+    if (kinds[a] >= DG_AGG_LONG_FIRST && kinds[a] <= DG_AGG_PAIR_TIME) return a;
+  return -1;
+}
+
+static int make_plan(const dg_scan* q, AggPlan* plan, FlPlan* fl) {
   if (q->n_aggs < 0 || q->n_aggs > kMaxAggs) return set_error(DG_ERR_UNSUPPORTED, "%d aggregators (max %d)", q->n_aggs, kMaxAggs);
   memset(plan, 0, sizeof *plan);
+  memset(fl, 0, sizeof *fl);
   plan->n = q->n_aggs;
   for (int a = 0; a < q->n_aggs; ++a) {
-    int k = q->aggs[a].kind;
-    if (k < DG_AGG_COUNT || k > DG_AGG_FLOAT_MAX) return set_error(DG_ERR_ARG, "aggregator kind %d", k);
+    const dg_agg& in = q->aggs[a];
+    int k = in.kind;
+    if (k < DG_AGG_COUNT || k > DG_AGG_PAIR_TIME) return set_error(DG_ERR_ARG, "aggregator kind %d", k);
+    fl->abi_kind[a] = k;
+    fl->aggs[a] = in;
+    if (is_first_last(k)) {
+      if (a + 1 >= q->n_aggs || q->aggs[a + 1].kind != DG_AGG_PAIR_TIME)
+        return set_error(DG_ERR_ARG, "aggregator %d (%s) is not followed by its DG_AGG_PAIR_TIME entry", a, agg_kind_name(k));
+      fl->any = true;
+      fl->field[a] = in.field;
+      fl->okind[a] = fl_value_kind(k);
+      k = fl_first(k) ? DG_AGG_LONG_MIN : DG_AGG_LONG_MAX;
+      fl->aggs[a].kind = k;
+      fl->aggs[a].field = nullptr;  // (its input is the key column, handed out by the engine)
+    } else if (k == DG_AGG_PAIR_TIME) {
+      if (a == 0 || !is_first_last(q->aggs[a - 1].kind))
+        return set_error(DG_ERR_ARG, "aggregator %d: DG_AGG_PAIR_TIME does not follow a first/last aggregator", a);
+      if (in.field || (in.filter && in.n_filter > 0))
+        return set_error(DG_ERR_ARG, "aggregator %d: DG_AGG_PAIR_TIME takes no field and no filter (it inherits its pair's)", a);
+      k = fl_first(q->aggs[a - 1].kind) ? DG_AGG_LONG_MIN : DG_AGG_LONG_MAX;
+      fl->okind[a] = k;
+      fl->aggs[a] = q->aggs[a - 1];  // the pair's filter
+      fl->aggs[a].kind = k;
+      fl->aggs[a].field = "__time";
+    } else {
+      fl->okind[a] = k;
+    }
     plan->kind[a] = k;
     plan->op[a] = slot_op(k);
   }
+  return DG_OK;
+}
+
+// The key budget of the first / last aggregators: row times [tmin, tmax] and cursor positions below
+// `positions` must fit bits(tmax - tmin) + bits(positions - 1) <= 63 (dg_firstlast.hip). *rb = the
+// position bits.
+static int fl_key_budget(const dg_scan* q, const FlPlan& fl, int64_t tmin, int64_t tmax, int64_t positions, int* rb) {
+  *rb = 0;
+  while (*rb < 63 && (1ll << *rb) < positions) ++*rb;
+  const uint64_t span = tmax >= tmin ? (uint64_t)tmax - (uint64_t)tmin : 0;
+  int tb = 0;
+  while (tb < 64 && (span >> tb)) ++tb;
+  if (tb + *rb > 63) {
+    int a = 0;
+    while (a < q->n_aggs && !is_first_last(fl.abi_kind[a])) ++a;
+    return set_error(DG_ERR_UNSUPPORTED, "%s(%s): row times spanning %d bits over %lld rows do not fit the 63-bit (time, row) key",
+                     agg_kind_name(fl.abi_kind[a]), fl.field[a] ? fl.field[a] : "", tb, (long long)positions);
+  }
+  return DG_OK;
+}
+
+// The segment's whole __time decoded for the key column (never time_view's representative times), and its
+// key column in the call's scratch presented as a one-block VIEW_LONG view (as Column::nd_ids is, with
+// log2_per = kNdLog2Per): *job is what k_fl_keys needs, launched by the caller after the decodes.
+static int fl_key_view(Segment* seg, CallScratch* cs, DecodeBatch* db, int64_t t0, int rb, int64_t p0, bool desc,
+                       FlKeyJob* job, ColView* keys, hipStream_t st) {
+  memset(job, 0, sizeof *job);
+  job->time.kind = VIEW_ABSENT;
+  const Column* tc = seg->find("__time");
+  if (tc) {
+    int rc = column_view(tc, cs, db, &job->time, st);
+    if (rc) return rc;
+  }
+  int64_t* col = dev_take<int64_t>(cs, (size_t)std::max<int64_t>(seg->nrows, 1) + 8);  // (padded past a quad)
+  const uint8_t** d_ptr;
+  const uint8_t** h_ptr = up_take<const uint8_t*>(cs, 1, &d_ptr, st);
+  if (!col || !h_ptr) return set_error(DG_ERR_OOM, "first/last key column of %lld rows", (long long)seg->nrows);
+  h_ptr[0] = reinterpret_cast<const uint8_t*>(col);
+  job->keys = col;
+  job->t0 = t0;
+  job->nrows = seg->nrows;
+  job->p0 = p0;
+  job->rb = rb;
+  job->desc = desc ? 1 : 0;
+  keys->blocks = d_ptr;
+  keys->log2_per = kNdLog2Per;
+  keys->width = 8;
+  keys->kind = VIEW_LONG;
+  keys->pad = 0;
   return DG_OK;
 }
 
@@ -2172,6 +2280,142 @@ static int agg_view(Segment* seg, const dg_agg& a, CallScratch* cs, DecodeBatch*
   return column_view(c, cs, db, v, st);
 }
 
+// The value column of a first/last slot as k_fl_resolve gathers from it: every block decoded to slots
+// (LZ4), viewed in place (UNCOMPRESSED / NONE) or expanded (DELTA / TABLE longs), like any aggregator
+// input; VIEW_ABSENT for a column the segment lacks (the selector then reads 0).
+static int fl_value_view(Segment* seg, const char* field, CallScratch* cs, DecodeBatch* db, ColView* v, hipStream_t st) {
+  dg_agg a;
+  memset(&a, 0, sizeof a);
+  a.kind = DG_AGG_LONG_SUM;
+  a.field = field;
+  const uint32_t* bits = nullptr;
+  return agg_view(seg, a, cs, db, v, &bits, st);
+}
+
+// The value view of a segment's k-th first/last slot (aggregator slot[k]): the view an earlier slot over the
+// same column already has (longFirst(x) and longLast(x) decode x once), else a new one.
+static int fl_shared_value_view(Segment* seg, const FlPlan& fl, const int32_t* slot, int k, ColView* val, CallScratch* cs,
+                                DecodeBatch* db, hipStream_t st) {
+  const char* f = fl.field[slot[k]];
+  for (int e = 0; e < k; ++e) {
+    const char* g = fl.field[slot[e]];
+    if (f && g && !strcmp(f, g)) {
+      val[k] = val[e];
+      return DG_OK;
+    }
+  }
+  return fl_value_view(seg, f, cs, db, &val[k], st);
+}
+
+// The smallest and largest row time of a segment: its first and last row's (a segment's rows are in time
+// order, the index's order: IndexMergerV9 writes them so and dg_segment_from_rows checks it), widened by the
+// attach-time block bounds of __time where they exist. Time-sorted rows are a precondition of the first /
+// last aggregators: a row before the first row's time in a segment without block bounds (UNCOMPRESSED /
+// NONE __time) would wrap its key and lose or win its cell wrongly (no access leaves a buffer: the resolve
+// masks and bounds the row).
+static void seg_time_range(const Segment* seg, int64_t* lo, int64_t* hi) {
+  *lo = seg->min_time;
+  *hi = seg->max_time;
+  const Column* tc = seg->find("__time");
+  if (!tc) return;
+  for (int64_t v : tc->data.min8) *lo = std::min(*lo, v);
+  for (int64_t v : tc->data.max8) *hi = std::max(*hi, v);
+}
+
+// The per-segment engines' (timeseries, topN) share of the first / last aggregators: segment i's key
+// column (t0 = its smallest row time, positions = its rows, reversed under a descending cursor), the
+// views of its first/last slots and their value columns. plan_seg fills vals[a] of every first/last
+// slot (the key view; their row bitsets come from agg_view as for any filtered aggregator), stage()
+// uploads the job tables, keys() / resolve() launch the two kernels.
+struct FlCall {
+  const FlPlan* fl = nullptr;
+  std::vector<FlKeyJob> kjobs;
+  std::vector<FlSeg> segs;
+  std::vector<FlResolveJob> rjobs;
+  FlKeyJob* d_kjobs = nullptr;
+  FlResolveJob* d_rjobs = nullptr;
+  int64_t max_rows = 0, max_pairs = 0;
+  int64_t key_bytes = 0;
+  std::vector<int64_t> seg_t0;  // per segment of the call (precheck): its smallest row time
+  std::vector<int> seg_rb;      // ... and its position bits
+
+  // The key budget of every segment with a cursor, checked before the call's first launch; plan_seg takes
+  // the segment's t0 and position bits from here.
+  int precheck(dg_segment* const* sgs, int n, const dg_scan* q, const Grain& gr) {
+    if (!fl->any) return DG_OK;
+    seg_t0.assign(n, 0);
+    seg_rb.assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+      const Segment* seg = reinterpret_cast<const Segment*>(sgs[i]);
+      if (!plan_cursors(seg, i, q, gr).any) continue;
+      int64_t hi;
+      seg_time_range(seg, &seg_t0[i], &hi);
+      const int rc = fl_key_budget(q, *fl, seg_t0[i], hi, seg->nrows, &seg_rb[i]);
+      if (rc) return rc;
+    }
+    return DG_OK;
+  }
+
+  int plan_seg(int i, Segment* seg, const dg_scan* q, bool desc, CallScratch* cs, DecodeBatch* db, ColView* vals,
+               hipStream_t st) {
+    const int64_t lo = seg_t0[i];
+    const int rb = seg_rb[i];
+    int rc;
+    FlKeyJob kj;
+    ColView keyv;
+    rc = fl_key_view(seg, cs, db, lo, rb, desc ? seg->nrows - 1 : 0, desc, &kj, &keyv, st);
+    if (rc) return rc;
+    FlSeg sg;
+    memset(&sg, 0, sizeof sg);
+    sg.nrows = (int32_t)seg->nrows;
+    sg.desc = desc ? 1 : 0;
+    FlResolveJob rj;
+    memset(&rj, 0, sizeof rj);
+    rj.rb = rb;
+    rj.nsegs = 1;
+    for (int a = 0; a < q->n_aggs; ++a) {
+      if (!is_first_last(fl->abi_kind[a])) continue;
+      vals[a] = keyv;
+      const int k = rj.nslots++;
+      rj.slot[k] = a;
+      rj.okind[k] = fl->okind[a];
+      rc = fl_shared_value_view(seg, *fl, rj.slot, k, sg.val, cs, db, st);
+      if (rc) return rc;
+    }
+    kjobs.push_back(kj);
+    segs.push_back(sg);
+    rjobs.push_back(rj);
+    max_rows = std::max<int64_t>(max_rows, seg->nrows);
+    key_bytes += 8 * seg->nrows;
+    return DG_OK;
+  }
+  // the last planned segment's cells: [ncells][rec] accumulator records
+  void cells(uint64_t* table, int64_t ncells, int rec) {
+    FlResolveJob& rj = rjobs.back();
+    rj.cells = table;
+    rj.ncells = ncells;
+    rj.cell_stride = rec;
+    rj.slot_stride = 1;
+    max_pairs = std::max<int64_t>(max_pairs, ncells * rj.nslots);
+  }
+  int stage(CallScratch* cs, hipStream_t st) {
+    if (kjobs.empty()) return DG_OK;
+    const size_t n = kjobs.size();
+    FlSeg* d_segs;
+    FlKeyJob* hk = up_take<FlKeyJob>(cs, n, &d_kjobs, st);
+    FlSeg* hs = up_take<FlSeg>(cs, n, &d_segs, st);
+    FlResolveJob* hr = up_take<FlResolveJob>(cs, n, &d_rjobs, st);
+    if (!hk || !hs || !hr) return set_error(DG_ERR_OOM, "first/last job tables");
+    for (size_t i = 0; i < n; ++i) rjobs[i].segs = d_segs + i;
+    memcpy(hk, kjobs.data(), sizeof(FlKeyJob) * n);
+    memcpy(hs, segs.data(), sizeof(FlSeg) * n);
+    memcpy(hr, rjobs.data(), sizeof(FlResolveJob) * n);
+    return DG_OK;
+  }
+  void keys(hipStream_t st) const { launch_fl_keys(d_kjobs, (int)kjobs.size(), max_rows, st); }
+  void resolve(hipStream_t st) const { launch_fl_resolve(d_rjobs, (int)rjobs.size(), max_pairs, st); }
+};
+
 // Timeseries decode fused with aggregation (BlockLayoutColumnarLongsSupplier.java:64-90 reads each
 // decompressed block in the loop that consumes it): the LZ4 blocks of an 8-byte long / double input
 // whose rows share one bucket inside the interval (time_block_buckets; every block when the cursor
@@ -2609,7 +2853,13 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
   if (rc) return rc;
   q = &qs;
   AggPlan plan;
-  rc = make_plan(q, &plan);
+  FlPlan fl;
+  rc = make_plan(q, &plan, &fl);
+  if (rc) return rc;
+  qs.aggs = fl.aggs;  // (the engine's aggregators: first/last pairs as their internal min / max slots)
+  FlCall flc;
+  flc.fl = &fl;
+  rc = flc.precheck(segs, n, q, gr);
   if (rc) return rc;
   CallGuard g(ctx);
   CallScratch* cs = g.cs;
@@ -2691,6 +2941,11 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
       if (rc) return rc;
       no_rows &= whole || (q->aggs[a].kind == DG_AGG_COUNT && !(q->aggs[a].filter && q->aggs[a].n_filter > 0));
     }
+    if (fl.any) {  // the first/last slots read the segment's key column (never a fused view)
+      rc = flc.plan_seg(i, seg, q, gr.desc, cs, &db, j.vals, st);
+      if (rc) return rc;
+      flc.cells(j.out, cur[i].nbuckets, rec);
+    }
     skip_scan[i] = no_rows ? 1 : 0;
     if (!no_rows && cur[i].nbuckets == 1) {  // one bucket: per-tile records + one fold (k_scan_combine)
       j.part = dev_take<uint64_t>(cs, (size_t)std::max<int64_t>((seg->nrows + kTileRows - 1) / kTileRows, 1) * rec);
@@ -2738,6 +2993,8 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
   ScanJob* h_jobs = up_take<ScanJob>(cs, n, &d_jobs, st);
   if (!h_jobs) return set_error(DG_ERR_OOM, "scan jobs");
   memcpy(h_jobs, jobs.data(), sizeof(ScanJob) * n);
+  rc = flc.stage(cs, st);
+  if (rc) return rc;
   if (!early) phase_event(ctx->ev[1], st);
   rc = run_decodes(cs, &db, st, nullptr, true);
   if (rc) return rc;
@@ -2747,6 +3004,7 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
   DG_CHECK_INTERRUPT(intr);
   DG_FLUSH(cs, st);  // (a no-op unless the decode staged nothing)
   phase_event(ctx->ev[3], st);
+  flc.keys(st);  // (after the __time decode, before the first aggregation kernel)
   launch_scan_agg(d_jobs, d_tile, ntiles, plan, 0, st);
   if (any_part) launch_scan_combine(d_jobs, n, plan, st);
   DG_CHECK_INTERRUPT(intr);
@@ -2781,6 +3039,7 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
     rc = fsum_pass(cs, gj, frows, bb + bits_for(n), false, plan, st, gr.desc);
     if (rc) return rc;
   }
+  flc.resolve(st);  // winning keys -> the pairs' values, while the decoded value columns are alive
   phase_event(ctx->ev[4], st);
   // results
   std::vector<uint64_t*> h_out(n, nullptr);
@@ -2810,7 +3069,7 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
       out_time[o] = q->period_ms ? gr.time_of(cur[i].bucket0 + b * q->period_ms) : cur[i].t_lo;
       out_rows[o] = (int64_t)h_out[i][b * rec];
       m.selected_rows += out_rows[o];
-      for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(plan.kind[a], h_out[i][b * rec + 1 + a]);
+      for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(fl.okind[a], h_out[i][b * rec + 1 + a]);
     }
   }
   float f1 = 0, f2 = 0, f3 = 0;
@@ -2926,7 +3185,13 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
   if (!dim && (t->metric_agg < 0 || t->metric_agg >= q->n_aggs)) return set_error(DG_ERR_ARG, "metric index");
   if (t->threshold <= 0) return set_error(DG_ERR_ARG, "threshold");
   AggPlan plan;
-  rc = make_plan(q, &plan);
+  FlPlan fl;
+  rc = make_plan(q, &plan, &fl);
+  if (rc) return rc;
+  qs.aggs = fl.aggs;  // (the engine's aggregators: first/last pairs as their internal min / max slots)
+  FlCall flc;
+  flc.fl = &fl;
+  rc = flc.precheck(segs, n, q, gr);
   if (rc) return rc;
   // what the dimension is over the segments with a cursor; everything unsupported is refused here,
   // before any launch
@@ -3022,6 +3287,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
   DecodeBatch db;
   decode_events(ctx, &db, false);
   bool any_multi = false;
+  std::vector<int> fl_job(n, -1);  // segment i's first/last resolve job
   phase_event(ctx->ev[0], st);
   for (int i = 0; i < n; ++i) {
     Segment* seg = reinterpret_cast<Segment*>(segs[i]);
@@ -3082,6 +3348,11 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
       rc = agg_view(seg, q->aggs[a], cs, &db, &j.vals[a], &j.agg_bits[a], st);
       if (rc) return rc;
     }
+    if (fl.any) {  // the first/last slots read the segment's key column
+      rc = flc.plan_seg(i, seg, q, gr.desc, cs, &db, j.vals, st);
+      if (rc) return rc;
+      fl_job[i] = (int)flc.rjobs.size() - 1;
+    }
     j.out = nullptr;  // allocated below with the bins
     tiles_rows[i] = seg->nrows;
   }
@@ -3107,6 +3378,14 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     jobs[i].nbounds = gr.nb + 1;
     jobs[i].out = dev_take<uint64_t>(cs, (size_t)nkeys * rec);
     if (!jobs[i].out) return set_error(DG_ERR_OOM, "topN table");
+    if (fl_job[i] >= 0) {
+      FlResolveJob& rj = flc.rjobs[fl_job[i]];
+      rj.cells = jobs[i].out;
+      rj.ncells = nkeys;
+      rj.cell_stride = rec;
+      rj.slot_stride = 1;
+      flc.max_pairs = std::max<int64_t>(flc.max_pairs, nkeys * rj.nslots);
+    }
     const int64_t nb = (nkeys + (1ll << shift) - 1) >> shift;
     for (int64_t k = 0; k < nb; ++k) bin_seg.push_back(i);
     cap += tiles_rows[i];
@@ -3178,7 +3457,8 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
   }
   // selection + gather of the candidates' records, all segments in one launch (staged before the
   // decode: its upload carries the bins', the scan's and the selection's tables)
-  const int mk = dim ? DG_AGG_COUNT : plan.kind[t->metric_agg];
+  // (a first/last metric: its slot holds the pair's value when the selection runs, k_fl_resolve)
+  const int mk = dim ? DG_AGG_COUNT : fl.okind[t->metric_agg];
   const int metric_agg = dim ? 0 : t->metric_agg;
   const int metric_op = (slot_op(mk) << 8) | mk;
   std::vector<TopnSelJob> sel;
@@ -3284,12 +3564,18 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     sel[k].hist = reinterpret_cast<uint32_t*>(d_selmem + sel_words * k + 41);
   }
   if (ns) memcpy(h_sel, sel.data(), sizeof(TopnSelJob) * ns);
+  rc = flc.stage(cs, st);
+  if (rc) return rc;
   rc = run_decodes(cs, &db, st, nullptr, true);
   ht.mark("decode_launched");
   if (rc) return rc;
   phase_event(ctx->ev[2], st);
   m.bytes_read = db.bytes;
   phase_event(ctx->ev[3], st);
+  if (fl.any) {  // (after the __time decode, before the first aggregation kernel)
+    DG_FLUSH(cs, st);
+    flc.keys(st);
+  }
   if (any_multi) {
     // multi-value dimension: per-(row, value) atomics into identity-initialised tables
     SlotInit init{};
@@ -3359,6 +3645,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     rc = fsum_pass(cs, gj, frows, bits_for(n) + bb + ib, true, plan, st, gr.desc);
     if (rc) return rc;
   }
+  flc.resolve(st);  // before the selection chain: a first/last aggregator may be the ordering metric
   if (ns) {
     DG_FLUSH(cs, st);
     launch_topn_select(d_sel, ns, max_card, na, metric_agg, metric_op, t->inverted, sel_threshold, st);
@@ -3469,7 +3756,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
           const int64_t o = out_base[k] * t->threshold + (int64_t)e;
           const uint64_t* r = sorted_at(k, e);
           out_ids[o] = (int32_t)r[0];
-          for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(plan.kind[a], r[2 + a]);
+          for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(fl.okind[a], r[2 + a]);
         }
         continue;
       }
@@ -3521,7 +3808,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
       for (size_t e = 0; e < res.size(); ++e) {
         const int64_t o = out_base[k] * t->threshold + (int64_t)e;
         out_ids[o] = h_cand[k][res[e]];
-        for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(plan.kind[a], h_tab[k][(size_t)res[e] * rec + 1 + a]);
+        for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(fl.okind[a], h_tab[k][(size_t)res[e] * rec + 1 + a]);
       }
       continue;
     }
@@ -3544,7 +3831,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
           const int64_t o = out_base[k] * t->threshold + (int64_t)nout++;
           const uint64_t* rr = sorted_at(k, e);
           out_ids[o] = (int32_t)rr[0];
-          for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(plan.kind[a], rr[2 + a]);
+          for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(fl.okind[a], rr[2 + a]);
         };
         for (int e = 0; e < g; ++e) emit(e);
         for (int e = g; e < nc && nout < K; ++e) {
@@ -3622,7 +3909,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     for (size_t e = 0; e < v.size(); ++e) {
       const int64_t o = out_base[k] * t->threshold + (int64_t)e;
       out_ids[o] = v[e].id;
-      for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(plan.kind[a], h_tab[k][(size_t)v[e].idx * rec + 1 + a]);
+      for (int a = 0; a < na; ++a) out_values[o * na + a] = finalize_slot(fl.okind[a], h_tab[k][(size_t)v[e].idx * rec + 1 + a]);
     }
   }
   ht.mark("replayed");
@@ -3981,7 +4268,30 @@ static uint64_t combine_abi(int kind, uint64_t a, uint64_t b) {
   }
 }
 
-// comparator key of an ABI-encoded metric value (Long.compare / Double.compare / Float.compare)
+// AggregatorFactory.combine over one record of ABI-encoded values, w = combine(w, v) (w the left side). A
+// first/last pair (the value's slot and, directly after it, its DG_AGG_PAIR_TIME slot) combines as a whole:
+// LongFirstAggregatorFactory.combine (LongFirstAggregatorFactory.java:103-112) keeps lhs when
+// lhs.time <= rhs.time, else rhs — the left side wins ties; LongLastAggregatorFactory.combine
+// (LongLastAggregatorFactory.java:107) keeps lhs when lhs.time > rhs.time, else rhs — the right side wins
+// ties (the double and float factories are the same).
+static void combine_abi_row(const AggPlan& plan, const FlPlan& fl, uint64_t* w, const uint64_t* v) {
+  for (int k = 0; k < plan.n; ++k) {
+    if (is_first_last(fl.abi_kind[k])) {  // (make_plan: slot k + 1 is its pair time)
+      const int64_t lt = (int64_t)w[k + 1], rt = (int64_t)v[k + 1];
+      const bool keep_lhs = fl_first(fl.abi_kind[k]) ? lt <= rt : lt > rt;
+      if (!keep_lhs) {
+        w[k] = v[k];
+        w[k + 1] = v[k + 1];
+      }
+      ++k;
+      continue;
+    }
+    w[k] = combine_abi(plan.kind[k], w[k], v[k]);
+  }
+}
+
+// comparator key of an ABI-encoded metric value (Long.compare / Double.compare / Float.compare; a
+// first/last aggregator's getComparator compares the pairs' values: pass its value kind, FlPlan::okind)
 static uint64_t abi_metric_key(int kind, uint64_t v, int inverted) {
   uint64_t k;
   if (kind == DG_AGG_COUNT || kind == DG_AGG_LONG_SUM || kind == DG_AGG_LONG_MIN || kind == DG_AGG_LONG_MAX) {
@@ -4023,11 +4333,12 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
   if (out_type != DG_COL_STRING && !is_numeric_type(out_type))
     return set_error(DG_ERR_UNSUPPORTED, "topN dimension %s: output type %d", t->dimension ? t->dimension : "", out_type);
   AggPlan plan;
-  int rc = make_plan(q, &plan);
+  FlPlan fl;
+  int rc = make_plan(q, &plan, &fl);
   if (rc) return rc;
   if (t->metric_agg < 0 || t->metric_agg >= plan.n) return set_error(DG_ERR_ARG, "metric index");
   if (t->threshold <= 0) return set_error(DG_ERR_ARG, "threshold");
-  const int na = plan.n, mk = plan.kind[t->metric_agg], nl = in->n_lists;
+  const int na = plan.n, mk = fl.okind[t->metric_agg], nl = in->n_lists;
   // the dimension column of every list's segment, resolved once (segment mode)
   std::vector<const Column*> lcol(nl > 0 ? nl : 1, nullptr);
   int num_type = 0;  // segment mode: DG_COL_* of a numeric dimension
@@ -4197,7 +4508,7 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
           vo += na;
         }
         uint64_t* w = const_cast<uint64_t*>(a.v);
-        for (int k = 0; k < na; ++k) w[k] = combine_abi(plan.kind[k], w[k], e.v[k]);
+        combine_abi_row(plan, fl, w, e.v);
         a.mkey = abi_metric_key(mk, w[ma], inv);
       } else {
         acc.push_back(e);
@@ -4598,6 +4909,8 @@ struct dg_result {
   std::vector<int32_t> cards;                         // dg_merge result: cluster dictionary sizes
   bool limited = false;                               // dg_result_limit: groups in the push-down order
   std::vector<int32_t> kinds;                         // DG_AGG_* of every aggregator (combine semantics)
+  std::vector<int32_t> abi_kinds;                     // the caller's kinds when they differ (first/last pairs:
+                                                      // `kinds` then has the value's type; such a result is not merged)
   dg_grouper_info grouper{};                          // what grouped it (dg_result_grouper_info)
   ~dg_result() {
     if (!ctx) return;
@@ -4675,10 +4988,46 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   if (nd < 0 || nd > kMaxGroupDims) return set_error(DG_ERR_UNSUPPORTED, "%d groupBy dimensions (max %d)", nd, kMaxGroupDims);
   if (n > kMaxCallSegs) return set_error(DG_ERR_UNSUPPORTED, "%d segments in one call (max %d)", n, kMaxCallSegs);
   AggPlan plan;
-  rc = make_plan(q, &plan);
+  FlPlan fl;
+  rc = make_plan(q, &plan, &fl);
   if (rc) return rc;
+  qs.aggs = fl.aggs;  // (the engine's aggregators: first/last pairs as their internal min / max slots)
   std::vector<Segment*> sv(n);
   for (int i = 0; i < n; ++i) sv[i] = reinterpret_cast<Segment*>(segs[i]);
+  // First / last aggregators: the call's segments merge in one sort, so the keys share one origin (the
+  // smallest row time of the segments with a cursor) and the position is the call-wide row reference
+  // row_base + r: earlier segments win first-ties, later ones last-ties (a left fold of combine in
+  // segment order). The budget is checked here, before any launch.
+  int64_t fl_t0 = 0;
+  int fl_rb = 0;
+  if (fl.any) {
+    int64_t lo = 0, hi = 0, total = 0;
+    bool seen = false;
+    for (int i = 0; i < n; ++i) {
+      if (!plan_cursors(sv[i], i, q, gr).any) continue;
+      int64_t l, h;
+      seg_time_range(sv[i], &l, &h);
+      lo = seen ? std::min(lo, l) : l;
+      hi = seen ? std::max(hi, h) : h;
+      seen = true;
+      total += sv[i]->nrows;
+    }
+    rc = fl_key_budget(q, fl, lo, hi, total, &fl_rb);
+    if (rc) return rc;
+    fl_t0 = lo;
+  }
+  std::vector<FlKeyJob> fl_kjobs;
+  std::vector<FlSeg> fl_segs;
+  FlResolveJob fl_rj;
+  memset(&fl_rj, 0, sizeof fl_rj);
+  fl_rj.rb = fl_rb;
+  fl_rj.abi = 1;
+  for (int a = 0; a < plan.n; ++a) {
+    if (!is_first_last(fl.abi_kind[a])) continue;
+    fl_rj.slot[fl_rj.nslots] = a;
+    fl_rj.okind[fl_rj.nslots++] = fl.okind[a];
+  }
+  int64_t fl_max_rows = 0, fl_run = 0;
   // string or long dimensions (dim_kind; what it refuses is refused here, before any launch)
   bool dim_long[kMaxGroupDims] = {};
   for (int d = 0; d < nd; ++d) {
@@ -4834,6 +5183,13 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   for (int i = 0; i < n; ++i) {
     GbJob& j = gj[i];
     memset(&j, 0, sizeof j);
+    if (fl.any) {  // (every segment of the call has its entry: the resolve finds a row's segment by row_base)
+      FlSeg sg;
+      memset(&sg, 0, sizeof sg);
+      sg.row_base = (uint32_t)fl_run;  // (= row_base[i]; a segment without a cursor holds no row: nrows stays 0)
+      if (cur[i].any) fl_run += sv[i]->nrows;
+      fl_segs.push_back(sg);
+    }
     if (!cur[i].any) continue;
     Segment* seg = sv[i];
     uint32_t* bits = nullptr;
@@ -4895,8 +5251,53 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
       rc = agg_view(seg, q->aggs[a], cs, &db, &j.vals[a], &j.agg_bits[a], st);
       if (rc) return rc;
     }
+    if (fl.any) {
+      // the first/last slots' payload field is the key; their value columns are no payload fields: they
+      // are decoded to slots (main stream) for the resolve
+      FlKeyJob kj;
+      ColView keyv;
+      rc = fl_key_view(seg, cs, &db, fl_t0, fl_rb, (int64_t)row_base[i], false, &kj, &keyv, st);
+      if (rc) return rc;
+      fl_kjobs.push_back(kj);
+      fl_max_rows = std::max<int64_t>(fl_max_rows, seg->nrows);
+      FlSeg& sg = fl_segs[i];
+      sg.nrows = (int32_t)seg->nrows;
+      for (int k = 0; k < fl_rj.nslots; ++k) {
+        j.vals[fl_rj.slot[k]] = keyv;
+        rc = fl_shared_value_view(seg, fl, fl_rj.slot, k, sg.val, cs, &db, st);
+        if (rc) return rc;
+      }
+    }
     rows[i] = seg->nrows;
   }
+  FlKeyJob* d_fl_kjobs = nullptr;
+  FlSeg* d_fl_segs = nullptr;
+  if (fl.any) {
+    FlKeyJob* hk = up_take<FlKeyJob>(cs, fl_kjobs.size(), &d_fl_kjobs, st);
+    FlSeg* hs = up_take<FlSeg>(cs, fl_segs.size(), &d_fl_segs, st);
+    if (!hk || !hs) return set_error(DG_ERR_OOM, "first/last job tables");
+    if (!fl_kjobs.empty()) memcpy(hk, fl_kjobs.data(), sizeof(FlKeyJob) * fl_kjobs.size());
+    if (!fl_segs.empty()) memcpy(hs, fl_segs.data(), sizeof(FlSeg) * fl_segs.size());
+  }
+  // winning keys of the result's first/last slot columns -> the pairs' values (k_fl_resolve), after the
+  // reduce (sort grouper: the group count is the device's) or the hash grouper's emit
+  auto fl_resolve = [&](uint64_t* slots, int64_t cap_, int64_t ncells, const uint32_t* n_ptr) -> int {
+    if (!fl.any || ncells <= 0) return DG_OK;
+    FlResolveJob* d_rj;
+    FlResolveJob* h_rj = up_take<FlResolveJob>(cs, 1, &d_rj, st);
+    if (!h_rj) return set_error(DG_ERR_OOM, "first/last job tables");
+    *h_rj = fl_rj;
+    h_rj->cells = slots;
+    h_rj->ncells = ncells;
+    h_rj->cell_stride = 1;
+    h_rj->slot_stride = cap_;
+    h_rj->n_ptr = n_ptr;
+    h_rj->segs = d_fl_segs;
+    h_rj->nsegs = (int32_t)fl_segs.size();
+    DG_FLUSH(cs, st);
+    launch_fl_resolve(d_rj, 1, ncells * fl_rj.nslots, st);
+    return DG_OK;
+  };
   ht.mark("views");
   DG_CHECK_INTERRUPT(intr);
   // The payload columns only meet the keys at the reduce: they decode on the side stream while the
@@ -5058,6 +5459,7 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
                         st);
   }
   phase_event(ctx->ev[3], st);
+  if (fl.any) launch_fl_keys(d_fl_kjobs, (int)fl_kjobs.size(), fl_max_rows, st);  // (__time is decoded; before the keygen)
   // The keygen fused into the first radix pass (launch_gb_sort_generated): the sort grouper over a
   // rows_elems call in row-ref mode with packed words, no time view (the bucket would need __time),
   // every dimension a single-value little-endian id view or missing, and the payload columns decoded
@@ -5127,7 +5529,8 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   res->period = q->period_ms;
   if (gr.hb) res->bounds.assign(gr.hb, gr.hb + gr.nb + 1);
   res->universal = q->interval_start;  // GroupByStrategyV2.getUniversalTimestamp (ALL granularity)
-  res->kinds.assign(plan.kind, plan.kind + na);
+  res->kinds.assign(fl.okind, fl.okind + na);  // (a resolved first/last slot column is a value of its type)
+  res->abi_kinds.assign(fl.abi_kind, fl.abi_kind + na);
   res->dicts = md;
   res->keys = static_cast<uint64_t*>(result_alloc(ctx, (size_t)cap * 8));
   res->slots = static_cast<uint64_t*>(result_alloc(ctx, (size_t)cap * rec * 8));
@@ -5148,6 +5551,8 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
       launch_gb_hash_collect(tab, &gsb, ngh, st);
       launch_radix_sort(&gsb, key_bits, st);
       launch_gb_hash_emit(&gsb, ngh, tab, plan, res->keys, res->slots, cap, st);
+      rc = fl_resolve(res->slots, cap, ngh, nullptr);
+      if (rc) return rc;
     }
     res->grouper.grouper = DG_GROUPER_HASH;
     res->grouper.table_slots = tab.capacity;
@@ -5171,6 +5576,8 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
     launch_gb_reduce(&sb, plan, res->keys, res->slots, cap, head_pos, carry_g, carry_slots, open_g, st);
     for (int a = 0; a < na; ++a)
       if (plan.kind[a] == DG_AGG_FLOAT_SUM) launch_fsum_runs(d_jobs, n, ntiles, &sb, plan, a, head_pos, res->slots, cap, st);
+    rc = fl_resolve(res->slots, cap, cap, sb.n + 1);
+    if (rc) return rc;
   }
   phase_event(ctx->ev[4], st);
   if (!use_hash) DG_HIP(hipMemcpyAsync(h_n, sb.n, 12, hipMemcpyDeviceToHost, st));  // selected rows, groups, run overflow
@@ -5205,6 +5612,8 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
     if (!sb.lb_status) return set_error(DG_ERR_OOM, "sort tables");
     launch_radix_sort(&sb, key_bits, st);
     launch_gb_reduce(&sb, plan, res->keys, res->slots, cap, nullptr, gb_carry_g, gb_carry_slots, gb_open_g, st);
+    rc = fl_resolve(res->slots, cap, cap, sb.n + 1);
+    if (rc) return rc;
     DG_HIP(hipMemcpyAsync(h_n, sb.n, 8, hipMemcpyDeviceToHost, st));
     rc = finish_call(cs, st);
     if (rc) return rc;
@@ -6345,14 +6754,19 @@ int dg_rowset_fetch(dg_rowset* rs, int32_t seg, int32_t col, int64_t start, int6
 void dg_rowset_release(dg_rowset* rs) { delete rs; }
 
 // ---- BufferAggregator records ----
+// (a first/last pair is two entries: the caller places the DG_AGG_PAIR_TIME slot at the pair's offset and
+// the value's slot 8 bytes after it, the reference's [time][value] record, LongFirstBufferAggregator.java:40-46)
+static bool records_f32(int k) {
+  return k == DG_AGG_FLOAT_SUM || k == DG_AGG_FLOAT_MIN || k == DG_AGG_FLOAT_MAX || k == DG_AGG_FLOAT_FIRST || k == DG_AGG_FLOAT_LAST;
+}
 int dg_records_pack(const uint64_t* slots, int64_t n, const dg_record_layout* lay, void* out) {
   if (n < 0 || !lay || (n > 0 && (!slots || !out)) || lay->n_aggs < 0 || (lay->n_aggs && (!lay->kinds || !lay->offsets)))
     return set_error(DG_ERR_ARG, "bad record layout");
   const int na = lay->n_aggs;
   for (int a = 0; a < na; ++a) {
     const int k = lay->kinds[a];
-    if (k < DG_AGG_COUNT || k > DG_AGG_FLOAT_MAX) return set_error(DG_ERR_ARG, "aggregator kind %d", k);
-    const int w = (k == DG_AGG_FLOAT_SUM || k == DG_AGG_FLOAT_MIN || k == DG_AGG_FLOAT_MAX) ? 4 : 8;
+    if (k < DG_AGG_COUNT || k > DG_AGG_PAIR_TIME) return set_error(DG_ERR_ARG, "aggregator kind %d", k);
+    const int w = records_f32(k) ? 4 : 8;
     if (lay->offsets[a] < 0 || lay->offsets[a] + w > lay->record_size)
       return set_error(DG_ERR_ARG, "aggregator %d at offset %d does not fit a %d-byte record", a, lay->offsets[a], lay->record_size);
   }
@@ -6363,7 +6777,7 @@ int dg_records_pack(const uint64_t* slots, int64_t n, const dg_record_layout* la
       const int k = lay->kinds[a];
       const uint64_t v = slots[i * na + a];
       uint8_t* p = rec + lay->offsets[a];
-      if (k == DG_AGG_FLOAT_SUM || k == DG_AGG_FLOAT_MIN || k == DG_AGG_FLOAT_MAX) {
+      if (records_f32(k)) {
         const uint32_t f = (uint32_t)v;  // the float's bits ride in the slot's low 4 bytes
         for (int b = 0; b < 4; ++b) p[b] = (uint8_t)(f >> (8 * (lay->big_endian ? 3 - b : b)));
       } else {
@@ -6375,10 +6789,19 @@ int dg_records_pack(const uint64_t* slots, int64_t n, const dg_record_layout* la
 }
 
 // ---- cross-device merge ----
+// The device-side groupBy merges combine slot by slot (k_merge_reduce); a first/last pair combines as a
+// whole by its times, which they do not do yet: refused before any work, naming the aggregator.
+static int refuse_pairs(const int32_t* kinds, int n, const char* what) {
+  const int a = kinds ? find_first_last(kinds, n) : -1;
+  if (a < 0) return DG_OK;
+  return set_error(DG_ERR_UNSUPPORTED, "%s: aggregator %d (%s) is a first/last pair, which the device-side groupBy merge does not combine",
+                   what, a, agg_kind_name(kinds[a]));
+}
 static int keyspace_layout(const dg_keyspace* ks, KeyLayout* lay, AggPlan* plan) {
   if (!ks || ks->n_dims < 0 || ks->n_dims > kMaxGroupDims || (ks->n_dims && !ks->card))
     return set_error(DG_ERR_ARG, "bad key space");
   if (ks->n_aggs < 0 || ks->n_aggs > kMaxAggs || (ks->n_aggs && !ks->agg_kinds)) return set_error(DG_ERR_ARG, "bad key space aggregators");
+  if (int prc = refuse_pairs(ks->agg_kinds, ks->n_aggs, "key space")) return prc;
   memset(lay, 0, sizeof *lay);
   lay->ndims = ks->n_dims;
   int shift = 0;
@@ -6415,6 +6838,7 @@ int dg_keyspace_bits(const dg_keyspace* ks, int32_t* bits) {
 
 int dg_result_export(dg_result* r, const dg_keyspace* ks, const int32_t* const* maps, uint64_t* d_keys, uint64_t* d_slots) {
   if (!r) return set_error(DG_ERR_ARG, "null result");
+  if (int prc = refuse_pairs(r->abi_kinds.data(), (int)r->abi_kinds.size(), "dg_result_export")) return prc;
   if (r->limited) return set_error(DG_ERR_ARG, "a limited result is not in key order");
   KeyLayout lay;
   AggPlan plan;
@@ -6648,6 +7072,7 @@ int dg_groupby_merge_devices(dg_result* const* parts, int32_t n_parts, dg_contex
   for (int32_t p = 0; p < n_parts; ++p) {
     const dg_result* r = parts[p];
     if (!r) return set_error(DG_ERR_ARG, "null part %d", p);
+    if (int prc = refuse_pairs(r->abi_kinds.data(), (int)r->abi_kinds.size(), "dg_groupby_merge_devices")) return prc;
     if (r->limited) return set_error(DG_ERR_ARG, "part %d is a limited result (not in key order)", p);
     if (r->dicts.empty() || (int)r->dicts.size() != r->ndims)
       return set_error(DG_ERR_ARG, "part %d is not a dg_groupby_run result", p);
@@ -6842,9 +7267,10 @@ int dg_timeseries_merge(const dg_scan* scan, int32_t n_lists, const int32_t* n, 
     return set_error(DG_ERR_ARG, "bad arguments");
   const int na = scan->n_aggs;
   if (na < 0 || na > kMaxAggs || (na && (!scan->aggs || (n_lists && !values)))) return set_error(DG_ERR_ARG, "bad aggregators");
-  for (int a = 0; a < na; ++a)
-    if (scan->aggs[a].kind < DG_AGG_COUNT || scan->aggs[a].kind > DG_AGG_FLOAT_MAX)
-      return set_error(DG_ERR_ARG, "aggregator kind %d", scan->aggs[a].kind);
+  AggPlan plan;
+  FlPlan fl;
+  const int prc = make_plan(scan, &plan, &fl);  // (kinds and the first/last pairs' entry order)
+  if (prc) return prc;
   const bool all = scan->period_ms == 0 && !scan->bucket_starts;
   struct E {
     int64_t t;
@@ -6872,7 +7298,7 @@ int dg_timeseries_merge(const dg_scan* scan, int32_t n_lists, const int32_t* n, 
       for (int a = 0; a < na; ++a) mv.push_back(values[at * na + a]);
     } else {
       uint64_t* acc = mv.data() + (mt.size() - 1) * na;
-      for (int a = 0; a < na; ++a) acc[a] = combine_abi(scan->aggs[a].kind, acc[a], values[at * na + a]);
+      combine_abi_row(plan, fl, acc, values + at * na);  // (acc: the earlier runner's side)
     }
     mr.back() += rows[at];
   }

@@ -746,6 +746,45 @@ void launch_nd_unique_emit(const uint64_t* words, int64_t n, const uint32_t* til
                            int64_t card, hipStream_t s);
 // ids[r] = lower bound of v[r] in vals[0 .. card)
 void launch_nd_encode(const ColView& v, int64_t nrows, const int64_t* vals, uint32_t card, uint32_t* ids, hipStream_t s);
+// ---- first / last aggregators (dg_firstlast.hip) ----
+// One segment's key column: keys[r] = ((((t(r) - t0) << rb) | p(r)) + 1) ^ sign, p(r) = p0 + r (ascending
+// cursor; groupBy: p0 = the segment's row_base) or p0 - r (descending: p0 = nrows - 1).
+struct FlKeyJob {
+  ColView time;   // the segment's __time, every block decoded (VIEW_ABSENT: every row at t0)
+  int64_t* keys;  // [nrows]
+  int64_t t0;
+  int64_t nrows;
+  int64_t p0;
+  int32_t rb;
+  int32_t desc;
+};
+void launch_fl_keys(const FlKeyJob* d_jobs, int njobs, int64_t max_rows, hipStream_t s);
+// A segment of a resolve: its rows' references are [row_base, row_base + nrows) and val[k] is the value
+// column of the job's k-th first/last slot in this segment (VIEW_ABSENT: the segment lacks it).
+struct FlSeg {
+  uint32_t row_base;
+  int32_t nrows;
+  int32_t desc;
+  int32_t pad;
+  ColView val[kMaxAggs];
+};
+// Cells whose first/last slots hold winning keys: slot a of cell c at
+// cells[c * cell_stride + (1 + a) * slot_stride] (accumulator tables: cell_stride = 1 + naggs, slot_stride = 1;
+// a groupBy result: 1 and its capacity). n_ptr (optional): the cell count known on the device only.
+struct FlResolveJob {
+  uint64_t* cells;
+  int64_t ncells;
+  int64_t cell_stride, slot_stride;
+  const uint32_t* n_ptr;
+  const FlSeg* segs;  // ascending row_base
+  int32_t nsegs;
+  int32_t rb;
+  int32_t abi;        // the slots are finalized (a groupBy result) and stay so
+  int32_t nslots;
+  int32_t slot[kMaxAggs];   // aggregator index of the k-th first/last slot
+  int32_t okind[kMaxAggs];  // DG_AGG_LONG_SUM / DOUBLE_SUM / FLOAT_SUM: the value's type
+};
+void launch_fl_resolve(const FlResolveJob* d_jobs, int njobs, int64_t max_pairs, hipStream_t s);
 // Row predicate of a filter on a numeric column: the reference evaluates it per row as a post-filter
 // (QueryableIndexStorageAdapter.makeCursors :244-260 -> FilteredOffset.java:40-105) through the
 // column's ValueMatcher ({Long,Float,Double}ValueMatcherColumnSelectorStrategy, the filters'

@@ -93,6 +93,15 @@ class GlobalDictionary:
         return GlobalDictionary(sorted(allv, key=R._java_key))
 
 
+def _refuse_pairs(query, what: str):
+    """A first/last aggregator's value is a (time, value) pair combined as a whole
+    (LongFirstAggregatorFactory.combine): the collectives here reduce slot by slot, so such a query is
+    refused before any collective or peer copy."""
+    for a in query.aggregations:
+        if a.is_pair:
+            raise R.N.UnsupportedQuery(2, f"{a.type}({a.name}): {what} does not combine first/last pairs")
+
+
 # ----------------------------------------------------------------------------------------------
 # timeseries
 # ----------------------------------------------------------------------------------------------
@@ -103,6 +112,7 @@ def allreduce_timeseries(dist, query: Q.TimeseriesQuery, local: List[Q.Result],
     `buckets` is the cluster-wide, identical-on-every-rank list of bucket keys (bucket starts; [0] for
     ALL granularity); None derives it with one all_gather_object of the local keys. Ranks without
     data for a bucket contribute identities."""
+    _refuse_pairs(query, "the cross-process timeseries reduce")
     torch, _ = _torch()
     dev = _device(dist)
     gran = query.granularity
@@ -194,6 +204,7 @@ def gather_topn(dist, query: Q.TopNQuery, raw: "R.TopNRaw", gdict: GlobalDiction
     A numeric topN dimension (a DimensionSpec output type other than STRING, or a LONG / FLOAT / DOUBLE
     column) is refused: its result ids index per-segment value lists, which have no cluster-wide
     dictionary here."""
+    _refuse_pairs(query, "the cross-process topN gather")
     if query.dimension_type != "STRING" or any(s.column_type(query.dimension) in R._NUMERIC_COLS
                                                for s in (segments or getattr(raw, "segments", None) or [])):
         raise R.N.UnsupportedQuery(2, f"topN on numeric dimension {query.dimension} across processes")
@@ -342,6 +353,7 @@ class GroupByExchange:
     SAMPLES = 256
 
     def __init__(self, dist, query: Q.GroupByQuery, segments, engine=None):
+        _refuse_pairs(query, "the cross-process groupBy merge")
         self.dist, self.query = dist, query
         self.world, self.rank = dist.get_world_size(), dist.get_rank()
         self.engine = engine if engine is not None else NativeMerge(segments[0].context)
@@ -499,6 +511,7 @@ def _from_bits(a, b):
 def gather_groupby(dist, query: Q.GroupByQuery, partial: R.GroupByPartial,
                    gdicts: Dict[str, GlobalDictionary]):
     """all_gather this rank's (already device-merged) groups; rank 0 returns merged columns."""
+    _refuse_pairs(query, "the cross-process groupBy gather")
     torch, _ = _torch()
     dev = _device(dist)
     nd, na = len(query.dimensions), len(query.aggregations)

@@ -503,9 +503,38 @@ PREDICATE_FILTERS = (RegexDimFilter, SearchQueryDimFilter, LikeDimFilter)
 AGG_KINDS = {
     "count": 0, "longSum": 1, "doubleSum": 2, "floatSum": 3, "longMin": 4, "longMax": 5,
     "doubleMin": 6, "doubleMax": 7, "floatMin": 8, "floatMax": 9,
+    # query/aggregation/first/*, query/aggregation/last/*: the value at the earliest / latest __time
+    "longFirst": 10, "longLast": 11, "doubleFirst": 12, "doubleLast": 13, "floatFirst": 14, "floatLast": 15,
 }
 AGG_OUTPUT = {0: "long", 1: "long", 4: "long", 5: "long", 2: "double", 6: "double", 7: "double",
-              3: "float", 8: "float", 9: "float"}
+              3: "float", 8: "float", 9: "float",
+              10: "long", 11: "long", 12: "double", 13: "double", 14: "float", 15: "float", 16: "long"}
+FIRST_KINDS = (10, 12, 14)
+LAST_KINDS = (11, 13, 15)
+PAIR_TIME_KIND = 16  # DG_AGG_PAIR_TIME: the native entry that follows a first/last aggregator (its pair's time)
+LONG_MAX = (1 << 63) - 1
+LONG_MIN = -(1 << 63)
+
+
+@dataclass(frozen=True)
+class SerializablePair:
+    """collections/SerializablePair<Long, Number>: what a first/last BufferAggregator.get returns,
+    lhs = the time, rhs = the value at that time. Un-finalized values of the first/last aggregators are
+    pairs; AggregatorFactory.finalize_computation returns rhs."""
+    lhs: int
+    rhs: object
+
+    def __eq__(self, o):
+        if not isinstance(o, SerializablePair) or self.lhs != o.lhs or type(self.rhs) is not type(o.rhs):
+            return False
+        if isinstance(self.rhs, float):  # bit for bit (-0.0 is not 0.0), every NaN equal to every NaN
+            if self.rhs != self.rhs or o.rhs != o.rhs:
+                return self.rhs != self.rhs and o.rhs != o.rhs
+            return struct.pack("<d", self.rhs) == struct.pack("<d", o.rhs)
+        return self.rhs == o.rhs
+
+    def __hash__(self):
+        return hash((self.lhs, repr(self.rhs)))
 
 
 def _f32(x: float) -> float:
@@ -553,12 +582,21 @@ class AggregatorFactory:
         return AGG_KINDS[self.type]
 
     @property
+    def is_pair(self) -> bool:
+        """A first/last aggregator: its un-finalized values are SerializablePair(time, value)."""
+        return self.kind in FIRST_KINDS or self.kind in LAST_KINDS
+
+    @property
     def output_type(self) -> str:
         return AGG_OUTPUT[self.kind]
 
     def initial(self):
         """Aggregator reset / BufferAggregator.init values."""
         k = self.kind
+        if k in FIRST_KINDS or k in LAST_KINDS:
+            # LongFirstBufferAggregator.init: (Long.MAX_VALUE, 0); LongLastBufferAggregator.init: (Long.MIN_VALUE, 0)
+            zero = 0 if self.output_type == "long" else 0.0
+            return SerializablePair(LONG_MAX if k in FIRST_KINDS else LONG_MIN, zero)
         if k in (0, 1):
             return 0
         if k == 4:
@@ -574,6 +612,10 @@ class AggregatorFactory:
     def combine(self, a, b):
         """AggregatorFactory.combine (e.g. LongSumAggregator.combineValues, FloatSumAggregator.java:40-43)."""
         k = self.kind
+        if k in FIRST_KINDS:  # LongFirstAggregatorFactory.combine (:103-112): the left side wins ties
+            return a if a.lhs <= b.lhs else b
+        if k in LAST_KINDS:  # LongLastAggregatorFactory.combine (:107): the right side wins ties
+            return a if a.lhs > b.lhs else b
         if k in (0, 1):
             return _wrap64(int(a) + int(b))
         if k == 4:
@@ -590,8 +632,16 @@ class AggregatorFactory:
         r = java_max(float(a), float(b))
         return _f32(r) if k == 9 else r
 
+    def finalize_computation(self, v):
+        """AggregatorFactory.finalizeComputation: a first/last pair's rhs (LongFirstAggregatorFactory.java:
+        finalizeComputation returns ((SerializablePair) object).rhs); every other aggregator's value as is."""
+        return v.rhs if isinstance(v, SerializablePair) else v
+
     def compare_key(self, v):
-        """Sort key realising the factory comparator (Long.compare / Doubles.compare)."""
+        """Sort key realising the factory comparator (Long.compare / Doubles.compare; a first/last
+        aggregator's VALUE_COMPARATOR compares the pairs' rhs with Longs / Doubles / Floats.compare)."""
+        if isinstance(v, SerializablePair):
+            v = v.rhs
         if self.output_type == "long":
             return (0, int(v))
         v = float(v)
@@ -627,6 +677,37 @@ class AggregatorFactory:
 def filtered(agg: AggregatorFactory, flt) -> AggregatorFactory:
     """FilteredAggregatorFactory(agg, filter)."""
     return AggregatorFactory.from_json({"type": "filtered", "filter": flt, "aggregator": agg})
+
+
+def native_aggregations(aggs: Sequence["AggregatorFactory"]) -> List["AggregatorFactory"]:
+    """The aggregator entries of a native call (dg_scan.aggs): every first/last aggregator is followed by
+    its DG_AGG_PAIR_TIME entry, whose slot carries the pair's time."""
+    out: List[AggregatorFactory] = []
+    for a in aggs:
+        out.append(a)
+        if a.is_pair:
+            out.append(_PairTime(a))
+    return out
+
+
+def native_index(aggs: Sequence["AggregatorFactory"]) -> List[int]:
+    """Native slot index of every aggregator's value (a pair's time is the slot after it)."""
+    out, at = [], 0
+    for a in aggs:
+        out.append(at)
+        at += 2 if a.is_pair else 1
+    return out
+
+
+class _PairTime(AggregatorFactory):
+    """The DG_AGG_PAIR_TIME entry of a first/last aggregator: internal to the native calls (no JSON form)."""
+
+    def __init__(self, pair: AggregatorFactory):
+        self.type, self.name, self.fieldName, self.filter = "pairTime", pair.name + "\x00time", None, None
+
+    @property
+    def kind(self) -> int:
+        return PAIR_TIME_KIND
 
 
 def count(name="count"):
@@ -667,6 +748,30 @@ def float_min(name, field_name=None):
 
 def float_max(name, field_name=None):
     return AggregatorFactory("floatMax", name, field_name or name)
+
+
+def long_first(name, field_name=None):
+    return AggregatorFactory("longFirst", name, field_name or name)
+
+
+def long_last(name, field_name=None):
+    return AggregatorFactory("longLast", name, field_name or name)
+
+
+def double_first(name, field_name=None):
+    return AggregatorFactory("doubleFirst", name, field_name or name)
+
+
+def double_last(name, field_name=None):
+    return AggregatorFactory("doubleLast", name, field_name or name)
+
+
+def float_first(name, field_name=None):
+    return AggregatorFactory("floatFirst", name, field_name or name)
+
+
+def float_last(name, field_name=None):
+    return AggregatorFactory("floatLast", name, field_name or name)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -49,21 +49,75 @@ from .segment import GpuSegment
 # ----------------------------------------------------------------------------------------------
 # slot decoding
 # ----------------------------------------------------------------------------------------------
+def _native_width(query) -> int:
+    """Slots per record of a native call: one per aggregator, two per first/last aggregator (the pair's
+    value, then its time: make_scan's DG_AGG_PAIR_TIME entry)."""
+    return sum(2 if a.is_pair else 1 for a in query.aggregations)
+
+
 def _decode_slots(aggs: Sequence[Q.AggregatorFactory], slots: np.ndarray) -> List[np.ndarray]:
-    """[n, naggs] uint64 ABI slots -> one typed column per aggregator."""
+    """[n, native width] uint64 ABI slots -> one typed column per aggregator; a first/last aggregator's
+    column holds SerializablePair(time, value) objects (its value slot and the pair-time slot after it),
+    built one by one in Python: for a groupBy result of millions of groups that loop dominates the fetch
+    (the other aggregators' columns are views of the slot rows)."""
+    def typed(col, out_type):  # (strided views of the slot rows; floats are narrowed)
+        if out_type == "long":
+            return col.view(np.int64)
+        if out_type == "double":
+            return col.view(np.float64)
+        return (col & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+
     out = []
-    for a, col in zip(aggs, slots.T):  # (strided views of the slot rows; floats are narrowed)
-        if a.output_type == "long":
-            out.append(col.view(np.int64))
-        elif a.output_type == "double":
-            out.append(col.view(np.float64))
-        else:
-            out.append((col & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32))
+    cols = slots.T
+    for a, at in zip(aggs, Q.native_index(aggs)):
+        v = typed(cols[at], a.output_type)
+        if a.is_pair:
+            pairs = np.empty(len(v), dtype=object)
+            for i, (t, x) in enumerate(zip(cols[at + 1].view(np.int64).tolist(), v.tolist())):
+                pairs[i] = Q.SerializablePair(t, x)
+            v = pairs
+        out.append(v)
     return out
 
 
 def _py(v, out_type):
+    if isinstance(v, Q.SerializablePair):
+        return v
     return int(v) if out_type == "long" else float(v)
+
+
+def finalize_results(query, results):
+    """FinalizeResultsQueryRunner (query/FinalizeResultsQueryRunner.java:84-120) at the top of the runner
+    chain: every aggregator's value through AggregatorFactory.finalizeComputation — a first/last pair
+    becomes its rhs. Results of a query without such aggregators are returned as they are."""
+    aggs = [a for a in getattr(query, "aggregations", []) if a.is_pair]
+    if not aggs:
+        return results
+    out = []
+    for r in results:
+        if isinstance(r, Q.Row):
+            ev = dict(r.event)
+            for a in aggs:
+                if a.name in ev:
+                    ev[a.name] = a.finalize_computation(ev[a.name])
+            out.append(Q.Row(r.timestamp, ev))
+            continue
+        if isinstance(r.value, list):
+            vals = []
+            for e in r.value:
+                e = dict(e)
+                for a in aggs:
+                    if a.name in e:
+                        e[a.name] = a.finalize_computation(e[a.name])
+                vals.append(e)
+            out.append(Q.Result(r.timestamp, vals))
+        else:
+            v = dict(r.value)
+            for a in aggs:
+                if a.name in v:
+                    v[a.name] = a.finalize_computation(v[a.name])
+            out.append(Q.Result(r.timestamp, v))
+    return out
 
 
 def _group_by_device(segments: Sequence[GpuSegment]) -> "OrderedDict[int, List[int]]":
@@ -106,7 +160,7 @@ def timeseries_per_segment(segments: Sequence[GpuSegment], query: Q.TimeseriesQu
         return [timeseries_per_segment([s], q, stats, cancel)[0] if q is not None else []
                 for s, q in zip(segments, split)]
     out: List[List[Q.Result]] = [[] for _ in segments]
-    na = len(query.aggregations)
+    na = _native_width(query)
     for _, idx in _group_by_device(segments).items():
         segs = [segments[i] for i in idx]
         cap = _bucket_cap(segs, query)
@@ -138,7 +192,7 @@ def run_timeseries(segments: Sequence[GpuSegment], query: Q.TimeseriesQuery,
     """QueryRunnerFactory.mergeRunners over segments on any devices: one dg_timeseries_run per device,
     then every segment's bucket list (in segment order) folded natively by dg_timeseries_merge
     (TimeseriesBinaryFn, ResultMergeQueryRunner order: time, then runner)."""
-    na = len(query.aggregations)
+    na = _native_width(query)
     groups = list(_group_by_device(segments).items())
     caps = {dev: _bucket_cap([segments[i] for i in idx], query) for dev, idx in groups}
     cap = max(caps.values()) if caps else 1
@@ -513,7 +567,8 @@ def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence
             t.min_rank = mins.ctypes.data
             keep.append(mins)
     else:
-        t.metric_agg = [a.name for a in query.aggregations].index(spec.metric)
+        # (the native slot of the metric's value: a first/last aggregator orders by its pair's rhs)
+        t.metric_agg = Q.native_index(query.aggregations)[[a.name for a in query.aggregations].index(spec.metric)]
         t.inverted = int(spec.type == "inverted")
         t.dim_order = -1
     return t, keep
@@ -524,16 +579,20 @@ def _check_topn(query: Q.TopNQuery):
 
 
 def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional[RunStats] = None,
-             cancel: Optional[ctypes.c_int32] = None) -> TopNRaw:
+             cancel: Optional[ctypes.c_int32] = None, descending: bool = False) -> TopNRaw:
     """One batched dg_topn_run_opts over segments that share a device (PooledTopNAlgorithm, or over a numeric
     dimension DimExtractionTopNAlgorithm, + TopNNumericResultBuilder per segment, threshold
-    max(threshold, minTopNThreshold)). cancel: a flag another thread may set (DG_ERR_INTERRUPTED)."""
+    max(threshold, minTopNThreshold)). cancel: a flag another thread may set (DG_ERR_INTERRUPTED).
+    descending: descending cursors (dg_scan.descending; a TopNQuery itself is never descending,
+    TopNQuery.java:74): every cursor's rows last to first, a segment's lists latest bucket first."""
     _check_topn(query)
     if len(_group_by_device(segments)) != 1:
         raise ValueError("topn_raw: segments must share one device")
-    na = len(query.aggregations)
+    na = _native_width(query)
     K = query.segment_threshold
     scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
+    if descending:
+        scan.descending = 1
     t, keep_t = _topn_struct(query, K, segments)
     n = len(segments)
     bcap = _bucket_cap(segments, query)
@@ -566,7 +625,7 @@ def topn_merge_raw(query: Q.TopNQuery, cnt: np.ndarray, keys: np.ndarray, vals: 
     """dg_topn_merge over lists ordered by (timestamp, index) (TopNQueryQueryToolChest merge order).
     Returns (timestamp, list index, keys, value slots) of the merged entries, or None when no list
     has a cursor. handles: per-list segment handles (segment mode) or None (global ids)."""
-    na = len(query.aggregations)
+    na = _native_width(query)
     live = [i for i in range(len(cnt)) if cnt[i] >= 0]
     if not live:
         return None
@@ -656,7 +715,7 @@ def merge_dimension_lists(query: Q.TopNQuery, lists: Sequence[Tuple[int, int, "c
 
 def _merge_topn_dimension(query: Q.TopNQuery, segments: Sequence[GpuSegment], raw: TopNRaw) -> List[Q.Result]:
     spec = query.metric
-    K, na = raw.K, len(query.aggregations)
+    K, na = raw.K, _native_width(query)
     live = sorted((i for i in range(len(segments)) if raw.cnt[i] >= 0), key=lambda i: (int(raw.ts[i]), i))
     orders = [segments[i].dim_order(query.dimension, spec.ordering, spec.inverted) for i in live]
     tie_free = not any(o is not None and o.has_ties for o in orders)
@@ -699,17 +758,19 @@ def run_topn(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
 
 
 def topn_per_segment(segments: Sequence[GpuSegment], query: Q.TopNQuery,
-                     stats: Optional[RunStats] = None) -> List[List[Q.Result]]:
-    """Per-segment results (what each segment's QueryRunner returns), as Result lists."""
+                     stats: Optional[RunStats] = None, descending: bool = False) -> List[List[Q.Result]]:
+    """Per-segment results (what each segment's QueryRunner returns), as Result lists.
+    descending: topn_raw's descending cursors."""
     _check_topn(query)
     split = segment_queries(query, segments)
     if split is not None:  # every segment on its own calendar chain
-        return [topn_per_segment([s], q, stats)[0] if q is not None else [] for s, q in zip(segments, split)]
+        return [topn_per_segment([s], q, stats, descending)[0] if q is not None else []
+                for s, q in zip(segments, split)]
     out: List[List[Q.Result]] = [[] for _ in segments]
-    na = len(query.aggregations)
+    na = _native_width(query)
     for _, idx in _group_by_device(segments).items():
         segs = [segments[i] for i in idx]
-        raw = topn_raw(segs, query, stats)
+        raw = topn_raw(segs, query, stats, descending=descending)
         K, bcap = raw.K, raw.bcap
         for k, i in enumerate(idx):
             seg = segs[k]
@@ -891,7 +952,7 @@ class GroupByResult:
         (every group's is the universal timestamp, the query interval's start). pool: pinned host
         memory (dg_host_alloc) the columns land in by DMA; the partial's arrays are views of it."""
         q = self.query
-        nd, na = len(q.dimensions), len(q.aggregations)
+        nd, na = len(q.dimensions), _native_width(q)
         count = self.groups - start if count is None else count
         all_gran = q.granularity.is_all and self.time_map is None
         if pool is not None:
@@ -989,7 +1050,7 @@ class GroupByResult:
                 sort = _limit_needs_sort(q)
             except ValueError:
                 return None
-            aggs = {a.name: i for i, a in enumerate(q.aggregations)}
+            aggs = {a.name: i for a, i in zip(q.aggregations, Q.native_index(q.aggregations))}  # (native slots)
             for c in ls.columns if sort else []:
                 if c.dimension in aggs:
                     cols.append((N.ORDER_AGG, aggs[c.dimension], c.direction == "descending", None))
@@ -1171,6 +1232,9 @@ def groupby_merge_devices(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     copies) and merges them there, every target concurrently. targets: the contexts owning the key
     ranges (default: every participating device's context, so no device funnels the others' groups);
     returns the per-target results in key order."""
+    for a in query.aggregations:  # (before any engine call or peer copy)
+        if a.is_pair:
+            raise N.UnsupportedQuery(2, f"{a.type}({a.name}): the device-side groupBy merge does not combine first/last pairs")
     groups = _group_by_device(segments)
     parts = []
     try:
@@ -1304,6 +1368,15 @@ def _java_minmax_reduce(col: np.ndarray, starts: np.ndarray, is_min: bool) -> np
 
 def _reduce(a: Q.AggregatorFactory, col: np.ndarray, starts: np.ndarray) -> np.ndarray:
     k = a.kind
+    if a.is_pair:  # a left fold of the factory's combine over each run, in partial (segment) order
+        out = np.empty(len(starts), dtype=object)
+        ends = list(starts[1:]) + [len(col)]
+        for g, (s0, s1) in enumerate(zip(starts.tolist(), ends)):
+            acc = col[s0]
+            for i in range(s0 + 1, int(s1)):
+                acc = a.combine(acc, col[i])
+            out[g] = acc
+        return out
     if k in (0, 1):
         return np.add.reduceat(col.astype(np.int64), starts)
     if k == 4:
@@ -1401,6 +1474,8 @@ def _having_eval(h: Q.HavingSpec, row: Q.Row) -> bool:
     if t == "dimSelector":  # DimensionSelectorHavingSpec.eval: emptyToNull on both sides
         return (row.event.get(h.dimension) or None) == (h.value or None)
     metric = row.event.get(h.aggregation)
+    if isinstance(metric, Q.SerializablePair):  # a first/last aggregator compares by its value
+        metric = metric.rhs
     if t == "equalTo" and metric is None and h.value is None:
         return True
     if h.value is None:
@@ -1502,7 +1577,7 @@ def having_program(query: Q.GroupByQuery, dictionary) -> Optional[List[Tuple[int
     of dimension d. A leaf on a name that is no aggregator folds to a constant, as _having_eval's
     `metric is None` does; a dimSelector looks its value up (null and "" are the null id, an absent value
     never matches)."""
-    aggs = {a.name: (i, a) for i, a in enumerate(query.aggregations)}
+    aggs = {a.name: (i, a) for a, i in zip(query.aggregations, Q.native_index(query.aggregations))}  # (native slots)
     ops: List[Tuple[int, int, int, int]] = []
 
     def const(b):
@@ -2191,4 +2266,4 @@ def run_query(query, segments: Sequence[GpuSegment], stats: Optional[RunStats] =
     runner = f.mergeRunners([f.createRunner(s) for s in segments])
     if stats is not None:
         runner.stats = stats
-    return runner.run(query)
+    return finalize_results(query, runner.run(query))
