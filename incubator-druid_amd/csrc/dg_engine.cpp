@@ -4905,7 +4905,9 @@ struct dg_result {
   dg::KeyLayout lay{};
   int64_t bucket0 = 0, period = 0, universal = 0;
   std::vector<int64_t> bounds;  // calendar granularity: the call's bucket starts (bucket index -> time)
-  std::vector<std::shared_ptr<dg::MergedDict>> dicts;  // empty for a dg_merge result (cluster ids)
+  std::vector<std::shared_ptr<dg::MergedDict>> dicts;  // one per dimension; unused by a dg_merge result (cluster ids)
+  bool own_dicts = false;  // `dicts` is the result's own (dg_groupby_run, dg_groupby_merge_devices): a groupBy
+                           // without dimensions has an empty list there too
   std::vector<int32_t> cards;                         // dg_merge result: cluster dictionary sizes
   bool limited = false;                               // dg_result_limit: groups in the push-down order
   std::vector<int32_t> kinds;                         // DG_AGG_* of every aggregator (combine semantics)
@@ -5532,6 +5534,7 @@ static int groupby_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q
   res->kinds.assign(fl.okind, fl.okind + na);  // (a resolved first/last slot column is a value of its type)
   res->abi_kinds.assign(fl.abi_kind, fl.abi_kind + na);
   res->dicts = md;
+  res->own_dicts = true;
   res->keys = static_cast<uint64_t*>(result_alloc(ctx, (size_t)cap * 8));
   res->slots = static_cast<uint64_t*>(result_alloc(ctx, (size_t)cap * rec * 8));
   res->cap = cap;
@@ -5872,7 +5875,7 @@ int dg_result_fetch_rows(dg_result* r, int64_t start, int64_t count, int64_t* ro
 
 int dg_result_dim_dictionary(const dg_result* r, int32_t dim, int64_t* offsets, char* bytes, int64_t* total) {
   if (!r || dim < 0 || dim >= r->ndims) return set_error(DG_ERR_ARG, "dimension index %d", dim);
-  if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
+  if (!r->own_dicts) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
   const MergedDict& d = *r->dicts[dim];
   int64_t t = 0;
   if (d.is_long) {  // the decimal text of each value (Long.toString), formatted here: the dictionary holds longs
@@ -5936,6 +5939,9 @@ int dg_result_limit(dg_result* r, const dg_limit* spec) {
     o.in_shift[o.nfields] = d < 0 ? lay.bucket_shift : lay.dim_shift[d];
     out -= o.bits[o.nfields];
     o.out_shift[o.nfields] = out;
+    // (a field of no bits is dropped below and its slot taken again: nothing of it may stay behind)
+    o.desc[o.nfields] = 0;
+    o.rank[o.nfields] = nullptr;
     if (d >= 0) {
       o.desc[o.nfields] = desc[d];
       if (rank[d]) {  // caller's comparator ranks over the result's dictionary ids, checked and uploaded
@@ -6253,13 +6259,13 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
 
 int32_t dg_result_dim_cardinality(const dg_result* r, int32_t dim) {
   if (!r || dim < 0 || dim >= r->ndims) return -1;
-  if (r->dicts.empty()) return r->cards[dim];
+  if (!r->own_dicts) return r->cards[dim];
   return (int32_t)r->dicts[dim]->card();
 }
 
 int dg_result_dim_type(const dg_result* r, int32_t dim, int32_t* column_type, int32_t* output_type) {
   if (!r || dim < 0 || dim >= r->ndims) return set_error(DG_ERR_ARG, "dimension index %d", dim);
-  if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
+  if (!r->own_dicts) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
   if (column_type) *column_type = r->dicts[dim]->is_long ? DG_COL_LONG : DG_COL_STRING;
   if (output_type) *output_type = r->dicts[dim]->out_type;
   return DG_OK;
@@ -6267,7 +6273,7 @@ int dg_result_dim_type(const dg_result* r, int32_t dim, int32_t* column_type, in
 
 int dg_result_dim_longs(const dg_result* r, int32_t dim, int64_t* out) {
   if (!r || dim < 0 || dim >= r->ndims) return set_error(DG_ERR_ARG, "dimension index %d", dim);
-  if (r->dicts.empty()) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
+  if (!r->own_dicts) return set_error(DG_ERR_ARG, "a merged result's dictionary is the caller's cluster dictionary");
   const MergedDict& d = *r->dicts[dim];
   if (!d.is_long) return set_error(DG_ERR_ARG, "dimension %d (%s) is a string dimension", dim, d.dim.c_str());
   if (!out && !d.longs.empty()) return set_error(DG_ERR_ARG, "null argument");
@@ -7074,7 +7080,7 @@ int dg_groupby_merge_devices(dg_result* const* parts, int32_t n_parts, dg_contex
     if (!r) return set_error(DG_ERR_ARG, "null part %d", p);
     if (int prc = refuse_pairs(r->abi_kinds.data(), (int)r->abi_kinds.size(), "dg_groupby_merge_devices")) return prc;
     if (r->limited) return set_error(DG_ERR_ARG, "part %d is a limited result (not in key order)", p);
-    if (r->dicts.empty() || (int)r->dicts.size() != r->ndims)
+    if (!r->own_dicts || (int)r->dicts.size() != r->ndims)
       return set_error(DG_ERR_ARG, "part %d is not a dg_groupby_run result", p);
     for (const auto& pd : r->dicts)  // (the dictionary union below compares strings)
       if (pd->is_long)
@@ -7238,6 +7244,7 @@ int dg_groupby_merge_devices(dg_result* const* parts, int32_t n_parts, dg_contex
     const int mrc = dg_merge(targets[t], &ks, static_cast<uint64_t*>(rk.p), static_cast<uint64_t*>(rs.p), n, &outs[t], &tm[t]);
     if (mrc) return mrc;
     outs[t]->dicts = udicts;  // the union dictionaries: the merged result fetches like a groupBy result
+    outs[t]->own_dicts = true;
     outs[t]->bounds = r0->bounds;
     return DG_OK;
   }, &errs);

@@ -232,23 +232,31 @@ def gather_topn(dist, query: Q.TopNQuery, raw: "R.TopNRaw", gdict: GlobalDiction
         if dist.get_rank() != 0:
             return None
         return R.merge_topn(query, [lst for g in gathered for lst in g])
-    S = len(raw.cnt)
-    cnt = raw.cnt.astype(np.int64)
+    world = dist.get_world_size()
+    mine = len(raw.cnt)
+    # all_gather moves equal-sized tensors: a rank with fewer segments than another pads its lists with
+    # cursorless ones (count -1), which the fold skips
+    sizes: List = [None] * world
+    dist.all_gather_object(sizes, mine)
+    S = max(sizes)
+    cnt = np.full(S, -1, dtype=np.int64)
+    cnt[:mine] = raw.cnt
+    lts = np.zeros(S, dtype=np.int64)
+    lts[:mine] = raw.ts
     gids = np.full((S, K), -1, dtype=np.int64)
-    for s in range(S):
+    for s in range(mine):
         c = int(cnt[s])
         if c > 0:
             gids[s, :c] = translations[s][raw.ids[s * K:s * K + c]]
-    vals = raw.vals.reshape(S, K, max(na, 1)).view(np.int64)
+    vals = np.zeros((S, K, max(na, 1)), dtype=np.int64)
+    vals[:mine] = raw.vals.reshape(mine, K, max(na, 1)).view(np.int64)
     dim_spec = query.metric if query.metric.type == "dimension" else None
     ties = np.zeros(S, dtype=np.int64)  # dimension orders: does the segment's order have ties
     if dim_spec is not None:
-        for s in range(S):
+        for s in range(mine):
             o = segments[s].dim_order(query.dimension, dim_spec.ordering, dim_spec.inverted) if segments else None
             ties[s] = int(o is not None and o.has_ties)
-    payload = torch.from_numpy(np.concatenate([raw.ts.astype(np.int64), cnt, gids.ravel(), vals.ravel(),
-                                               ties])).to(dev)
-    world = dist.get_world_size()
+    payload = torch.from_numpy(np.concatenate([lts, cnt, gids.ravel(), vals.ravel(), ties])).to(dev)
     bufs = [torch.empty_like(payload) for _ in range(world)]
     dist.all_gather(bufs, payload)
     if dist.get_rank() != 0:

@@ -34,6 +34,13 @@ factor, so two correct sides differ by at most 2 gamma(n) A. Every other cell is
 aggregates, min / max (with the sign of zero), every sum over x (multiples of 0.125, |x| <= 8: exact in
 float32 too) and over l, timestamps, dimension values and the row order.
 
+The merge draw (merge_queries()): the queries the cross-segment, cross-device and cross-rank merges are held
+to — every ts-* and tn-*, the gb-* that do not group by v, and MERGE_GB further groupBy draws gm-* from
+default_rng([SEED, 3, index, attempt]) with v taken out of the dimension pool (no device-side merge takes a
+LONG dimension), a few pinned (MERGE_PINS). They run over the same rows as four segments (piece_paths: each
+fixture segment cut once at row n // 2, in layout 0), and their expectation is the oracle over those four
+(expected_for(q, PIECES)): the steering and empty-result redraws of a gm-* draw are evaluated there.
+
 Deviations from the plan this generator was written to, each forced by the engine's arithmetic:
 * the key+reference sort words need key bits + row-reference bits > 64; with 33,578 rows (16 bits) and the
   fixture's cardinalities (hi 15 bits, mid 9, v 10, hn 6) an hourly bucket (7 bits) gives 63. The four
@@ -127,41 +134,70 @@ def columns(i):
     return c
 
 
+def _spec(W, c):
+    """Rows given as columns()-style arrays / lists as a writer.SegmentSpec (nope is in none)."""
+    dims = {k: W.encode_strings(c[k]) for k in ("lo", "mid", "hi", "hn", "v_s")}
+    dims["tags"] = W.encode_multi_strings(c["tags"])
+    metrics = {"v": ("long", c["v"]), "l": ("long", c["l"]), "d": ("double", c["d"]), "d_abs": ("double", c["d_abs"]),
+               "f": ("float", c["f"]), "f_abs": ("float", c["f_abs"]), "x": ("double", c["x"])}
+    return W.SegmentSpec(timestamps=c["t"], dims=dims, metrics=metrics)
+
+
 def fixture_specs(W):
     """The two segments as writer.SegmentSpec (nope is in neither)."""
+    return [_spec(W, columns(i)) for i in range(len(ROWS))]
+
+
+PIECES = "pieces"  # the `layout` of the four-segment form of the fixture
+
+
+def piece_specs(W):
+    """The same rows as four segments: each fixture segment cut once at row n // 2 (the rows are time-sorted
+    with duplicate instants, so a cut may part equal timestamps). Every piece has its own dictionaries."""
     out = []
-    for i in range(len(ROWS)):
+    for i, n in enumerate(ROWS):
         c = columns(i)
-        dims = {k: W.encode_strings(c[k]) for k in ("lo", "mid", "hi", "hn", "v_s")}
-        dims["tags"] = W.encode_multi_strings(c["tags"])
-        metrics = {"v": ("long", c["v"]), "l": ("long", c["l"]), "d": ("double", c["d"]), "d_abs": ("double", c["d_abs"]),
-                   "f": ("float", c["f"]), "f_abs": ("float", c["f_abs"]), "x": ("double", c["x"])}
-        out.append(W.SegmentSpec(timestamps=c["t"], dims=dims, metrics=metrics))
+        for a, b in ((0, n // 2), (n // 2, n)):
+            out.append(_spec(W, {k: x[a:b] for k, x in c.items()}))
     return out
 
 
 _STATE = {"base": None, "paths": {}, "oracle": {}}
 
 
+def _write(name, specs, layout):
+    _, W, _ = _mods()
+    if _STATE["base"] is None:
+        _STATE["base"] = tempfile.mkdtemp(prefix="querygen_")
+        atexit.register(shutil.rmtree, _STATE["base"], ignore_errors=True)
+    bitmap, comp, kw = LAYOUTS[layout]
+    return [W.write_segment(os.path.join(_STATE["base"], "%s_s%d" % (name, i)), s, bitmap=bitmap, compression=comp,
+                            lz4_mode="fast", **kw) for i, s in enumerate(specs(W))]
+
+
 def layout_paths(k):
     """The segment directories of layout k (LAYOUTS), written at first use into a directory removed at exit."""
     if k not in _STATE["paths"]:
-        _, W, _ = _mods()
-        if _STATE["base"] is None:
-            _STATE["base"] = tempfile.mkdtemp(prefix="querygen_")
-            atexit.register(shutil.rmtree, _STATE["base"], ignore_errors=True)
-        bitmap, comp, kw = LAYOUTS[k]
-        _STATE["paths"][k] = [W.write_segment(os.path.join(_STATE["base"], "l%d_s%d" % (k, i)), s, bitmap=bitmap,
-                                              compression=comp, lz4_mode="fast", **kw)
-                              for i, s in enumerate(fixture_specs(W))]
+        _STATE["paths"][k] = _write("l%d" % k, fixture_specs, k)
     return _STATE["paths"][k]
+
+
+def piece_paths():
+    """The four pieces' directories, in layout 0 (the merges do not depend on the layout)."""
+    if PIECES not in _STATE["paths"]:
+        _STATE["paths"][PIECES] = _write("p", piece_specs, 0)
+    return _STATE["paths"][PIECES]
 
 
 def oracle_segments(k=0):
     if k not in _STATE["oracle"]:
         _, _, O = _mods()
-        _STATE["oracle"][k] = [O.OracleSegment(p) for p in layout_paths(k)]
+        _STATE["oracle"][k] = [O.OracleSegment(p) for p in (piece_paths() if k == PIECES else layout_paths(k))]
     return _STATE["oracle"][k]
+
+
+def piece_oracle_segments():
+    return oracle_segments(PIECES)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -540,7 +576,7 @@ def _draw_groupby(rng, force):
         dims = list(force["dims"])
     else:
         nd = int(rng.integers(0, 5))
-        pool = list(GB_DIMS)
+        pool = list(force.get("pool", GB_DIMS))
         dims = []
         while len(dims) < nd:
             d = pool.pop(int(rng.integers(0, len(pool))))
@@ -561,7 +597,7 @@ def _draw_groupby(rng, force):
     hk = force.get("having") or _pick(rng, ("none", "none", "none", "leaf", "leaf", "and", "or", "not"))
     having = None
     if hk != "none":
-        pre = _oracle_run(oracle_query(Q.query_from_json(js)))
+        pre = _oracle_run(oracle_query(Q.query_from_json(js)), force.get("layout", 0))
         n_leaf = 1 if hk in ("leaf", "not") else 2
         leaves = [_having_leaf(rng, tags, js, names, pre, aggs_by_name) for _ in range(n_leaf)]
         if all(x is not None for x in leaves):
@@ -605,10 +641,10 @@ def _draw_groupby(rng, force):
     if int(rng.integers(0, 5)) == 0:
         ctx["bufferGrouperMaxSize"] = 1_000_000
         tags.add("gb:ctx:maxsize")
-    if "limit" in js.get("limitSpec", {}) and having is None and int(rng.integers(0, 3)) == 0:
+    if "limit" in js.get("limitSpec", {}) and having is None and (int(rng.integers(0, 3)) == 0 or force.get("pushdown")):
         ctx["forceLimitPushDown"] = True
         tags.add("gb:ctx:pushdown")
-    if int(rng.integers(0, 5)) == 0:
+    if int(rng.integers(0, 5)) == 0 or force.get("dimsfirst"):
         ctx["sortByDimsFirst"] = True
         tags.add("gb:ctx:dimsfirst")
     if ctx:
@@ -666,14 +702,17 @@ def queries():
     return list(_GEN["queries"])
 
 
-def axes():
-    """id -> the axis values the query was drawn with."""
+def axes(merge=False):
+    """id -> the axis values the query was drawn with (merge: of the merge queries, the gm-* draws included)."""
     queries()
-    return _GEN["axes"]
+    if not merge:
+        return _GEN["axes"]
+    both = dict(_GEN["axes"], **_merge_gen()["axes"])
+    return {qid: both[qid] for qid, _ in merge_queries()}
 
 
 def query(qid):
-    return dict(queries())[qid]
+    return dict(merge_queries() if qid.startswith("gm") else queries())[qid]
 
 
 def ids(kind=None):
@@ -691,6 +730,74 @@ def queries_sha256():
 
 
 # ---------------------------------------------------------------------------------------------
+# the merge draw: the queries the cross-segment, cross-device and cross-rank merges are held to, over the
+# four pieces (expected_for(q, PIECES): a topN's per-segment cut and fold order depend on the split)
+# ---------------------------------------------------------------------------------------------
+MERGE_GB = 44  # gm-*: further groupBy draws that no device-side merge refuses (no dimension over v)
+MERGE_POOL = tuple(d for d in GB_DIMS if d not in ("vL", "vS"))
+# the gb-* indices that do not group by v (a draw's outcome, kept here so that ids need no generation;
+# tests/test_querygen.py holds it to the draw)
+GB_NO_V = (6, 7, 8, 9, 10, 11, 15, 19, 21, 23, 26, 27, 28, 29, 30, 32, 38, 40, 41, 43, 45, 49, 50, 51, 52, 56, 58, 59, 60, 61, 62)
+# index -> forced axis values: what the merge census of tests/test_querygen.py asks for among the queries of a
+# fixed-period granularity, the ones dg_groupby_merge_devices takes
+MERGE_PINS = {
+    0: {"dims": (), "g": "all"}, 1: {"dims": (), "g": "all", "hash": True}, 2: {"dims": (), "g": "all", "iv": "cut"},
+    3: {"dims": (), "g": "all", "iv": "empty"},
+    4: {"dims": ("mid", "lo"), "g": "hour", "having": "none", "limit": "order+limit", "pushdown": True},
+    5: {"dims": ("hi",), "g": "all", "having": "none", "limit": "only", "pushdown": True},
+    6: {"dims": ("tags", "hn"), "g": "dur", "having": "none", "limit": "order+limit", "pushdown": True},
+    7: {"dims": ("lo", "nope"), "g": "all", "having": "none", "limit": "only", "pushdown": True},
+    8: {"g": "hour", "iv": "empty"},
+}
+# id -> reason: a ts / tn / gb query whose floating sums steer its result within their bound on the pieces only
+# (at most 4; gm-* draws are drawn again instead)
+MERGE_LEFT_OUT = {}
+_MGEN = {}
+
+
+def _merge_gen():
+    if "queries" in _MGEN:
+        return _MGEN
+    Q, _, _ = _mods()
+    out, axes = [], {}
+    for i in range(MERGE_GB):
+        qid = "gm-%03d" % i
+        force = dict(MERGE_PINS.get(i, {}), pool=MERGE_POOL, layout=PIECES)
+        for attempt in range(MAX_ATTEMPTS):
+            js, tags = _draw_groupby(np.random.default_rng([SEED, 3, i, attempt]), force)
+            q = Q.query_from_json(js)
+            if steering_violations(q, PIECES):
+                continue
+            if not is_empty(expected_for(q, PIECES)) or tags & {"iv:empty", "f:nothing"}:
+                break
+        else:
+            raise AssertionError(f"{qid}: no draw in {MAX_ATTEMPTS} attempts keeps its floating sums apart")
+        out.append((qid, q))
+        axes[qid] = tags
+    _MGEN["queries"], _MGEN["axes"] = out, axes
+    return _MGEN
+
+
+def merge_ids(kind=None):
+    """The merge queries' ids, without generating anything: every ts-* and tn-*, the gb-* that do not group by
+    v, every gm-*, less MERGE_LEFT_OUT."""
+    out = ids("ts") + ids("tn") + ["gb-%03d" % i for i in GB_NO_V] + ["gm-%03d" % i for i in range(MERGE_GB)]
+    return [qid for qid in out if qid not in MERGE_LEFT_OUT and kind in (None, qid[:2])]
+
+
+def merge_queries():
+    """[(id, query)] of merge_ids()."""
+    old = dict(queries())
+    new = dict(_merge_gen()["queries"])
+    return [(qid, new[qid] if qid in new else old[qid]) for qid in merge_ids()]
+
+
+def merge_queries_sha256():
+    import hashlib
+    return hashlib.sha256("".join(qid + json.dumps(q.to_json(), sort_keys=True) for qid, q in merge_queries()).encode()).hexdigest()
+
+
+# ---------------------------------------------------------------------------------------------
 # floating sums that steer a result
 # ---------------------------------------------------------------------------------------------
 def _adjacent_violations(cells, what):
@@ -705,9 +812,9 @@ def _adjacent_violations(cells, what):
     return out
 
 
-def steering_violations(q):
+def steering_violations(q, layout=0):
     """Where a bounded floating sum decides q's result — a topN metric, a limit-spec column, a having operand —
-    the oracle's cells must be further apart than four times the bound. Returns the violations found."""
+    the oracle's cells (over `layout`) must be further apart than four times the bound. Returns the violations found."""
     Q, _, _ = _mods()
     aggs = {a.name: a for a in q.aggregations}
     out = []
@@ -715,7 +822,7 @@ def steering_violations(q):
         name = q.metric.metric if q.metric.type in ("numeric", "inverted") else None
         if name is None or not is_bounded(aggs[name]):
             return out
-        full = _oracle_run(dataclasses.replace(oracle_query(q), threshold=100_000))
+        full = _oracle_run(dataclasses.replace(oracle_query(q), threshold=100_000), layout)
         for r in full:
             out += _adjacent_violations([(e[name], cell_bound(aggs[name], e)) for e in r.value], f"metric {name} at {r.timestamp}")
         return out
@@ -737,7 +844,7 @@ def steering_violations(q):
         return out
     ctx = {k: x for k, x in oq.context.items() if k != "forceLimitPushDown"}
     if leaves:
-        pre = _oracle_run(dataclasses.replace(oq, limitSpec=None, having=None, context=ctx))
+        pre = _oracle_run(dataclasses.replace(oq, limitSpec=None, having=None, context=ctx), layout)
         for h in leaves:
             a = aggs[h.aggregation]
             for r in pre:
@@ -746,7 +853,7 @@ def steering_violations(q):
                     out.append(f"having {h.aggregation} {h.type} {h.value!r}: cell {r.event[a.name]!r} within 4 x {b!r}")
                     break
     if cols:
-        rows = _oracle_run(dataclasses.replace(oq, limitSpec=None, context=ctx))  # (after the having spec)
+        rows = _oracle_run(dataclasses.replace(oq, limitSpec=None, context=ctx), layout)  # (after the having spec)
         one = q.granularity.is_all or q._ctx_bool("sortByDimsFirst", False)
         for name in cols:
             groups = {}

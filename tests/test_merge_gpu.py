@@ -72,6 +72,18 @@ class LoopbackDist:
         for b, x in zip(bufs, self._exchange(t.clone())):
             b.copy_(x)
 
+    class ReduceOp:
+        SUM, MIN, MAX = "sum", "min", "max"
+
+    def all_reduce(self, t, op=ReduceOp.SUM):
+        """In place, folded in rank order in the tensor's own type (a float32 sum adds in float32)."""
+        import torch
+        got = self._exchange(t.clone())
+        acc = got[0].clone()
+        for x in got[1:]:
+            acc = acc + x if op == self.ReduceOp.SUM else (torch.minimum if op == self.ReduceOp.MIN else torch.maximum)(acc, x)
+        t.copy_(acc)
+
     def all_to_all_single(self, out, inp, out_splits=None, in_splits=None):
         import torch
         w = self.hub.world

@@ -6,7 +6,8 @@ layout, and the oracle's floating sums against math.fsum.
 Wall time of the 160 expectations on the development machine (one core, `gen` below: the generation runs
 every query on the oracle, a steered one a second time without its limit spec): 62 - 67 s for the generation,
 0.02 - 1.4 s per query, 0.4 s on average; the 140 s buckets over 33,578 rows and the 30,000-row results are
-the slow ones."""
+the slow ones. The merge draw (44 more groupBy queries on the four-piece form of the fixture) and the piece
+expectations of all 171 merge queries add 43 s and about 90 s; the module takes 200 s in all."""
 import copy
 import dataclasses
 import json
@@ -224,6 +225,90 @@ def test_oracle_sums_against_fsum(Q, O, gen):
             cancel = min(cancel, abs(exact) / total)
     print("oracle error / bound, worst group: %.4f; smallest |sum| / sum|x|: %.2e" % (worst, cancel))
     assert cancel < 1e-2
+
+
+# ---- the merge draw (querygen.merge_queries) and the four-piece form of the fixture ----
+MERGE_SHA256 = "4ea4ffcbf041e0a02a33868bdcd373c5211f0204e25b25889a52dadc4df3d193"
+
+
+@pytest.fixture(scope="module")
+def merge_gen(gen):
+    return G.merge_queries()
+
+
+def test_pieces_hold_the_fixture_rows(O):
+    """Each fixture segment cut once at row n // 2: the pieces' rows, two and two, are their segment's, and at
+    least one cut parts rows of one instant."""
+    whole, pieces = G.oracle_segments(), G.piece_oracle_segments()
+    assert [p.num_rows for p in pieces] == [n for r in G.ROWS for n in (r // 2, r - r // 2)]
+    parted = 0
+    for i, s in enumerate(whole):
+        a, b = pieces[2 * i], pieces[2 * i + 1]
+        assert np.array_equal(np.concatenate([a.time(), b.time()]), s.time())
+        for name, kind in (("l", "long"), ("d", "double"), ("f", "float")):
+            assert np.array_equal(np.concatenate([a.numeric(name, kind), b.numeric(name, kind)]), s.numeric(name, kind))
+        vals = [np.array(p.dictionary("hi"), dtype=object)[p.ids("hi")] for p in (a, b)]
+        assert np.array_equal(np.concatenate(vals), np.array(s.dictionary("hi"), dtype=object)[s.ids("hi")])
+        assert set(a.dictionary("hi")) != set(b.dictionary("hi"))  # every piece has its own dictionaries
+        parted += int(a.time()[-1] == b.time()[0])
+    print("cuts between rows of one instant:", parted)
+
+
+def test_merge_draw_is_deterministic(gen, merge_gen):
+    first = _json(merge_gen)
+    G._MGEN.clear()
+    assert _json(G.merge_queries()) == first
+    assert [qid for qid, _ in first] == G.merge_ids()
+    assert G.merge_queries_sha256() == MERGE_SHA256
+    # every ts-* and tn-*, the gb-* that do not group by v (GB_NO_V is the draw's outcome), every gm-*
+    no_v = tuple(int(qid[3:]) for qid, a in G.axes().items() if qid.startswith("gb") and not a & {"gb:dim:vL", "gb:dim:vS"})
+    assert G.GB_NO_V == no_v
+    assert len(G.MERGE_LEFT_OUT) <= 4, G.MERGE_LEFT_OUT
+    assert set(G.merge_ids()) | set(G.MERGE_LEFT_OUT) == \
+        set(G.ids("ts") + G.ids("tn")) | {"gb-%03d" % i for i in no_v} | {"gm-%03d" % i for i in range(G.MERGE_GB)}
+    old = dict(gen[0])
+    assert all(q.to_json() == old[qid].to_json() for qid, q in merge_gen if not qid.startswith("gm"))
+    assert not [qid for qid, q in merge_gen if qid[0] == "g" and "v" in q.dimensions]
+    assert not [qid for qid, q in merge_gen if any(a.is_pair for a in q.aggregations)]
+
+
+def test_merge_census(merge_gen):
+    """What the merge planes need to meet, counted over the groupBy merge queries of a fixed-period granularity
+    (the ones dg_groupby_merge_devices takes; a calendar one may be split per segment and merged on the host)."""
+    axes = G.axes(merge=True)
+    assert list(axes) == G.merge_ids()
+    gb = {qid: a for qid, a in axes.items() if qid[:2] in ("gb", "gm")}
+    fixed = {qid: a for qid, a in gb.items() if a & {"g:all", "g:hour", "g:dur"}}
+    assert len(gb) >= 60 and len(fixed) >= 40, (len(gb), len(fixed))
+    having = tuple("gb:having:" + k for k in ("gt", "lt", "eq", "dimsel", "and", "or", "not"))
+    wanted = {"zero dimensions under all": ("gb:ndims:0", "g:all"),
+              "zero dimensions under hour or dur": ("gb:ndims:0", ("g:hour", "g:dur")),
+              "tags": ("gb:dim:tags",), "nope": ("gb:dim:nope",), "forceHashAggregation": ("gb:ctx:hash",),
+              "having with a limit": (having, ("gb:limit:only", "gb:limit:order+limit")),
+              "forceLimitPushDown": ("gb:ctx:pushdown",), "sortByDimsFirst": ("gb:ctx:dimsfirst",),
+              "empty interval or nothing-filter": (("iv:empty", "f:nothing"),)}
+    counts = {what: len(_with(fixed, *w)) for what, w in wanted.items()}
+    print(len(gb), len(fixed), counts)
+    assert not {what: n for what, n in counts.items() if n < 4}, counts
+
+
+def test_pieces_answer_as_the_two_segments(Q, merge_gen):
+    """The oracle over the four pieces against the oracle over the two segments, for every timeseries and
+    groupBy merge query: floating sums over d / f within cell_bound (the pieces add in another order), every
+    other cell, the rows and their order exactly. (A topN's answer depends on the split: its per-segment cut
+    and fold order are the reference's.)"""
+    n = 0
+    for qid, q in merge_gen:
+        if not isinstance(q, Q.TopNQuery):
+            G.assert_parity(qid, q, G.expected_for(q, G.PIECES), G.expected_for(q), "pieces", "oracle")
+            n += 1
+    assert n == len(G.merge_ids()) - len(G.merge_ids("tn"))
+
+
+def test_no_steering_on_the_pieces(merge_gen):
+    """Every merge query keeps its steering floating sums apart on the piece expectation too."""
+    for qid, q in merge_gen:
+        assert G.steering_violations(q, G.PIECES) == [], qid
 
 
 def test_comparison_finds_what_it_should(Q, gen):
