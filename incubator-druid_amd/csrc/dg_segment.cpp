@@ -526,7 +526,7 @@ Lz4Job lz4_job(const BlockColumn& b, int32_t k, uint8_t* dst, int32_t expect, in
 }
 
 namespace {
-static void index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host);
+static int index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host);
 
 
 // The column's attach-time decode tables (BlockColumn.job_desc / kind_list): a query then plans its
@@ -1063,7 +1063,7 @@ int parse_string(Context* ctx, Column* c, Slice s) {
     }
     if (!c->bm_bytes.alloc(host.size())) return set_error(DG_ERR_OOM, "hipMalloc bitmaps");
     DG_HIP(hipMemcpy(c->bm_bytes.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    index_bitmap_pieces(c, host);
+    return index_bitmap_pieces(c, host);
   }
   return DG_OK;
 }
@@ -1072,29 +1072,34 @@ int parse_string(Context* ctx, Column* c, Slice s) {
 // workgroups: a Concise bitmap into runs of kConcisePieceWords words with the row each run starts
 // at (the sum of the earlier words' spans: 31 rows per literal, 31 * (blocks) per fill,
 // ConciseSetUtils.java:45-75), a Roaring bitmap into its containers (portable format: cookie,
-// [run bitmap], key / cardinality descriptors, [offsets], containers). A bitmap whose header does not
-// parse stays whole (the per-bitmap kernel reports it).
+// [run bitmap], key / cardinality descriptors, [offsets], containers). Every non-empty Roaring bitmap's
+// headers are walked here, whatever its size, and one that does not parse fails the attach with
+// DG_ERR_FORMAT: k_roaring_or and k_roaring_pieces follow the offsets and run counts without checking
+// them, so they only ever see bitmaps whose every read stays inside their bytes.
 static uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 static uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
+// The containers of one Roaring bitmap appended to *out (when given); false when the cookie is unknown
+// or the descriptors, the offset header, a container's start or size, or a run count leave the bytes.
+// The empty bitmap (no-run cookie, 0 containers, 8 bytes) is legal and has no containers.
 static bool roaring_containers(const uint8_t* p, int len, std::vector<BmPiece>* out, int64_t base_off) {
   if (len < 8) return false;
   const uint32_t cookie = le32(p);
-  int pos = 4, n = 0;
+  int64_t pos = 4, n = 0;
   const uint8_t* runbits = nullptr;
   bool has_off = true;
   if ((cookie & 0xFFFFu) == 12347u) {
-    n = (int)(cookie >> 16) + 1;
+    n = (int64_t)(cookie >> 16) + 1;
     runbits = p + pos;
     pos += (n + 7) / 8;
     has_off = n >= 4;
   } else if (cookie == 12346u) {
-    n = (int)le32(p + 4);
+    n = (int64_t)le32(p + 4);
     pos = 8;
   } else {
     return false;
   }
-  if (n <= 0 || pos + 4 * n > len) return false;
+  if (pos + 4 * n > len) return false;
   const uint8_t* desc = p + pos;
   pos += 4 * n;
   const uint8_t* offs = nullptr;
@@ -1103,23 +1108,24 @@ static bool roaring_containers(const uint8_t* p, int len, std::vector<BmPiece>* 
     offs = p + pos;
     pos += 4 * n;
   }
-  int cur = pos;
+  int64_t cur = pos;
   std::vector<BmPiece> v;
-  for (int c = 0; c < n; ++c) {
+  for (int64_t c = 0; c < n; ++c) {
     const int key = (int)le16(desc + 4 * c), card = (int)le16(desc + 4 * c + 2) + 1;
     const bool run = runbits && ((runbits[c >> 3] >> (c & 7)) & 1);
-    const int start = offs ? (int)le32(offs + 4 * c) : cur;
-    if (start < 0 || start + 2 > len) return false;
-    const int sz = run ? 2 + 4 * (int)le16(p + start) : (card <= 4096 ? 2 * card : 8192);
+    const int64_t start = offs ? (int64_t)le32(offs + 4 * c) : cur;
+    if (start < pos || start + 2 > len) return false;
+    const int64_t sz = run ? 2 + 4 * (int64_t)le16(p + start) : (card <= 4096 ? 2 * card : 8192);
     if (start + sz > len) return false;
-    v.push_back(BmPiece{base_off + start, (int64_t)key << 16, sz, (int32_t)((uint32_t)(card - 1) | (run ? 0x80000000u : 0u))});
+    v.push_back(BmPiece{base_off + start, (int64_t)key << 16, (int32_t)sz,
+                        (int32_t)((uint32_t)(card - 1) | (run ? 0x80000000u : 0u))});
     cur = start + sz;
   }
-  out->insert(out->end(), v.begin(), v.end());
+  if (out) out->insert(out->end(), v.begin(), v.end());
   return true;
 }
 
-static void index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host) {
+static int index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host) {
   const int n = (int)c->bm_off.size();
   std::vector<int32_t> first(n + 1, 0);
   std::vector<BmPiece> pieces;
@@ -1139,8 +1145,11 @@ static void index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host) {
           row += (w & 0x80000000u) ? 31 : 31ll * ((int64_t)(w & 0x01FFFFFFu) + 1);
         }
       }
-    } else if (len > kRoaringSplitBytes) {
-      roaring_containers(p, len, &pieces, c->bm_off[i]);
+    } else if (len > 0) {
+      // pieces only for a bitmap over the split size; a shorter one is checked and stays whole
+      if (!roaring_containers(p, len, len > kRoaringSplitBytes ? &pieces : nullptr, c->bm_off[i]))
+        return set_error(DG_ERR_FORMAT, "%s: Roaring bitmap %d (%d bytes) is truncated or corrupt", c->name.c_str(), i,
+                         len);
     }
   }
   first[n] = (int32_t)pieces.size();
@@ -1148,6 +1157,7 @@ static void index_bitmap_pieces(Column* c, const std::vector<uint8_t>& host) {
     c->bm_piece_first.swap(first);
     c->bm_pieces.swap(pieces);
   }
+  return DG_OK;
 }
 
 int64_t column_device_bytes(const Column& c) {

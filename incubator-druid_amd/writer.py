@@ -372,8 +372,17 @@ def roaring_bitmaps(ids: np.ndarray, cardinality: int) -> List[bytes]:
     return [roaring_serialize(np.sort(order[bounds[v]:bounds[v + 1]])) for v in range(cardinality)]
 
 
+def encoded_bitmaps(rows_of_value: Sequence[np.ndarray], num_rows: int, bitmap_encoder) -> List[bytes]:
+    """One bitmap per dictionary value from a caller's encoder: ``bitmap_encoder(rows, num_rows) -> bytes``
+    with rows the value's ascending int64 row numbers. The bytes are written as they are (any legal
+    encoding of the rows, or on purpose an illegal one), in the column's bitmap type."""
+    return [bytes(bitmap_encoder(np.ascontiguousarray(r, dtype=np.int64), num_rows)) for r in rows_of_value]
+
+
 def string_column_part(dictionary: List[Optional[str]], ids: np.ndarray, bitmap: str,
-                       compression: str, lz4_mode: str, num_bytes: Optional[int] = None) -> bytes:
+                       compression: str, lz4_mode: str, num_bytes: Optional[int] = None,
+                       bitmap_encoder=None) -> bytes:
+    """bitmap_encoder: see encoded_bitmaps; None writes the canonical Concise / Roaring bytes."""
     card = len(dictionary)
     dict_vals = [None if (v is None or v == "") else v.encode("utf-8") for v in dictionary]
     # null / "" are both stored as a zero-length value (NullHandling.replaceWithDefault)
@@ -389,7 +398,11 @@ def string_column_part(dictionary: List[Optional[str]], ids: np.ndarray, bitmap:
         out = bytes([0x02]) + struct.pack(">i", 0)  # COMPRESSED, flags = 0 (single-value, bitmaps)
         out += generic_indexed(dict_vals, sorted_flag=True)
         out += ids_part(ids, card, compression, lz4_mode, num_bytes)
-    if bitmap == "concise":
+    if bitmap_encoder is not None:
+        order = np.argsort(ids, kind="stable")
+        bounds = np.searchsorted(ids[order], np.arange(card + 1))
+        bms = encoded_bitmaps([order[bounds[v]:bounds[v + 1]] for v in range(card)], len(ids), bitmap_encoder)
+    elif bitmap == "concise":
         bms = concise_bitmaps(ids, card)
     else:
         bms = roaring_bitmaps(ids, card)
@@ -408,7 +421,7 @@ def encode_multi_strings(rows: Sequence[Sequence[Optional[str]]]) -> Tuple[List[
 
 
 def multi_string_column_part(dictionary: List[Optional[str]], rows: Sequence[np.ndarray], bitmap: str,
-                             compression: str, lz4_mode: str, legacy: bool = False) -> bytes:
+                             compression: str, lz4_mode: str, legacy: bool = False, bitmap_encoder=None) -> bytes:
     """Multi-value dictionary-encoded column (DictionaryEncodedColumnPartSerde.java:183-217):
     compressed = version COMPRESSED + MULTI_VALUE_V3 flag, ids as V3CompressedVSizeColumnarMultiInts
     ([0x03][CompressedColumnarInts row start offsets + end][CompressedVSizeColumnarInts values],
@@ -453,7 +466,9 @@ def multi_string_column_part(dictionary: List[Optional[str]], rows: Sequence[np.
         rws = np.unique(sr[bounds[v]:bounds[v + 1]])
         if v == 0 and len(empty_rows):
             rws = np.union1d(rws, empty_rows)
-        if bitmap == "concise":
+        if bitmap_encoder is not None:
+            bms.extend(encoded_bitmaps([rws], len(rows), bitmap_encoder))
+        elif bitmap == "concise":
             bms.append(_tools.concise_encode(rws).astype(">i4").tobytes())
         else:
             bms.append(roaring_serialize(rws))
@@ -512,14 +527,18 @@ class SegmentSpec:
 
 def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", compression: str = "lz4",
                   dim_compression: Optional[str] = None, lz4_mode: str = "hc", long_encoding: str = "longs",
-                  id_bytes: Optional[int] = None, legacy_multi_value: bool = False, check_sorted: bool = True) -> str:
+                  id_bytes: Optional[int] = None, legacy_multi_value: bool = False, check_sorted: bool = True,
+                  bitmap_encoder=None) -> str:
     """Write a v9 segment directory. Rows must already be in segment order (time-sorted).
     long_encoding: IndexSpec.longEncoding, "longs" (default) or "auto" (DELTA / TABLE / LONGS per column,
     __time included: IndexMergerV9 serializes it with the same long encoding).
     id_bytes: width of single-value dictionary ids (default: numBytes for the cardinality).
     legacy_multi_value: compressed multi-value dimensions in the pre-V3 CompressedVSizeColumnarMultiInts form.
     check_sorted=False: write rows out of time order (robustness tests of the engine only; IndexMergerV9
-    never writes such a segment)."""
+    never writes such a segment).
+    bitmap_encoder: a callable (ascending int64 rows, num_rows) -> bytes that encodes every dictionary
+    value's bitmap in place of the canonical encoder (other legal forms of the same rows; see
+    encoded_bitmaps). None: the canonical bytes."""
     os.makedirs(out_dir, exist_ok=True)
     n = len(spec.timestamps)
     ts = np.asarray(spec.timestamps, dtype=np.int64)
@@ -537,14 +556,16 @@ def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", comp
             part = {"type": "stringDictionary", "bitmapSerdeFactory": _bitmap_json(bitmap),
                     "byteOrder": "LITTLE_ENDIAN"}
             files[name] = _descriptor("STRING", part, multi=True) + multi_string_column_part(
-                dictionary, [np.asarray(r, dtype=np.int32) for r in ids], bitmap, dim_comp, lz4_mode, legacy_multi_value)
+                dictionary, [np.asarray(r, dtype=np.int32) for r in ids], bitmap, dim_comp, lz4_mode, legacy_multi_value,
+                bitmap_encoder)
             continue
         ids = np.asarray(ids, dtype=np.int32)
         if len(ids) != n:
             raise ValueError(f"dimension {name} has {len(ids)} rows, expected {n}")
         part = {"type": "stringDictionary", "bitmapSerdeFactory": _bitmap_json(bitmap), "byteOrder": "LITTLE_ENDIAN"}
+        hook = {} if bitmap_encoder is None else {"bitmap_encoder": bitmap_encoder}
         files[name] = _descriptor("STRING", part) + string_column_part(dictionary, ids, bitmap, dim_comp, lz4_mode,
-                                                                       id_bytes)
+                                                                       id_bytes, **hook)
     for name, (kind, vals) in spec.metrics.items():
         vals = np.asarray(vals)
         if len(vals) != n:

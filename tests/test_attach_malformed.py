@@ -1,5 +1,5 @@
-"""Attach-time validation of segment bytes (GenericIndexed offsets, truncated column parts): a corrupt
-segment is rejected with DG_ERR_FORMAT (the reference throws IAE / ISE from GenericIndexed.java:131-149
+"""Attach-time validation of segment bytes (GenericIndexed offsets, truncated column parts, Roaring
+bitmap headers): a corrupt segment is rejected with DG_ERR_FORMAT (the reference throws IAE / ISE from GenericIndexed.java:131-149
 when a header does not fit its buffer) instead of reading outside the mapped file."""
 import ctypes
 import importlib
@@ -99,6 +99,142 @@ def test_short_literal_only_block_rejected(tmp_path, W):
     h = ctypes.c_void_p()
     rc = N.lib().dg_segment_attach(ctx.handle, bad.encode(), ctypes.byref(h))
     assert rc == 1 and "literal-only block" in N.lib().dg_last_error().decode(), (rc, N.lib().dg_last_error())
+
+
+def _roaring_starts(data):
+    """(container count, position of the offset header or None, container start positions) of a legal
+    Roaring bitmap (RoaringFormatSpec)."""
+    cookie = struct.unpack_from("<I", data, 0)[0]
+    if cookie & 0xFFFF == 12347:
+        n = (cookie >> 16) + 1
+        runbits = [(data[4 + i // 8] >> (i % 8)) & 1 for i in range(n)]
+        pos = 4 + (n + 7) // 8
+        has_off = n >= 4
+    else:
+        n, runbits, pos, has_off = struct.unpack_from("<I", data, 4)[0], None, 8, True
+    cards = [struct.unpack_from("<H", data, pos + 4 * i + 2)[0] + 1 for i in range(n)]
+    pos += 4 * n
+    offs_at = pos if has_off else None
+    pos += 4 * n if has_off else 0
+    starts = []
+    for i in range(n):
+        starts.append(pos)
+        if runbits and runbits[i]:
+            pos += 2 + 4 * struct.unpack_from("<H", data, pos)[0]
+        else:
+            pos += 2 * cards[i] if cards[i] <= 4096 else 8192
+    assert pos == len(data)
+    return n, offs_at, starts, runbits
+
+
+def _truncated(data):  # the last container loses its last 3 bytes
+    return data[:-3]
+
+
+def _offset_past_end(data):  # the last container's offset points beyond the bitmap
+    n, offs_at, _, _ = _roaring_starts(data)
+    b = bytearray(data)
+    b[offs_at + 4 * (n - 1):offs_at + 4 * n] = struct.pack("<I", len(data) + 4096)
+    return bytes(b)
+
+
+def _run_count_too_large(data):  # the last container, a run container, claims 65535 runs
+    _, _, starts, runbits = _roaring_starts(data)
+    assert runbits[-1]
+    b = bytearray(data)
+    b[starts[-1]:starts[-1] + 2] = struct.pack("<H", 0xFFFF)
+    return bytes(b)
+
+
+def _headers_overrun(data):  # a container count whose descriptors alone are longer than the bitmap
+    b = bytearray(data)
+    if struct.unpack_from("<I", data, 0)[0] & 0xFFFF == 12347:
+        b[2:4] = struct.pack("<H", 0xFFFF)  # 65536 containers
+    else:
+        b[4:8] = struct.pack("<I", 0x01000000)
+    return bytes(b)
+
+
+def _bad_cookie(data):
+    return struct.pack("<I", 12345) + data[4:]
+
+
+def test_unreadable_roaring_bitmaps_rejected(tmp_path, Q, W):
+    """Every Roaring bitmap's headers are walked at attach (the filter path's k_roaring_or and
+    k_roaring_pieces follow offsets and run counts unchecked): a bitmap that is truncated mid-container,
+    has an offset past its end, a run count too large for its bytes, a container count whose headers
+    overrun it, or an unknown cookie fails the attach with DG_ERR_FORMAT, below the 32 KiB split size
+    and above it. No query is run on a corrupt segment: it is attached and nothing more."""
+    import bitmap_variants as BV
+    N = importlib.import_module("incubator-druid_amd._native")
+    S = importlib.import_module("incubator-druid_amd.segment")
+    ctx = S.GpuContext.get(0)
+
+    def write(name, spec, target, corrupt, encode):
+        """Value `target` (told by its first row) gets corrupt(encode(rows)), the others encode(rows)."""
+        first = int(np.flatnonzero(np.asarray(spec.dims["d"][1]) == target)[0])
+        seen = []
+
+        def enc(rows, num_rows):
+            data = encode(rows, num_rows)
+            if int(rows[0]) != first:
+                return data
+            seen.append(len(data))
+            return corrupt(data)
+        path = W.write_segment(str(tmp_path / name), spec, bitmap="roaring", compression="none", bitmap_encoder=enc)
+        assert len(seen) == 1
+        return path, seen[0]
+
+    def must_reject(path, what):
+        h = ctypes.c_void_p()
+        rc = N.lib().dg_segment_attach(ctx.handle, path.encode(), ctypes.byref(h))
+        assert rc == 1, (what, rc, N.lib().dg_last_error())  # (an attached corrupt segment is left alone)
+        assert b"Roaring bitmap" in N.lib().dg_last_error(), (what, N.lib().dg_last_error())
+
+    # a 3-value dimension: "a" two long runs (run containers, run cookie, no offset header), "b" every
+    # 97th row elsewhere (array containers, offset header), "c" the rest
+    n = 100_000
+    r = np.arange(n)
+    a = ((r >= 100) & (r < 30_000)) | ((r >= 70_000) & (r < 90_000))
+    b = ~a & (r % 97 == 0)
+    ids = np.where(a, 0, np.where(b, 1, 2)).astype(np.int32)
+    small = W.SegmentSpec(timestamps=r.astype(np.int64), dims={"d": (["a", "b", "c"], ids)},
+                          metrics={"m": ("long", r % 7)}, interval=(0, n))
+    good, _ = write("good", small, 0, lambda data: data, BV.roaring_canonical)
+    assert open(os.path.join(good, "00000.smoosh"), "rb").read() == \
+        open(os.path.join(W.write_segment(str(tmp_path / "plain"), small, bitmap="roaring", compression="none"),
+                          "00000.smoosh"), "rb").read()
+    g = S.GpuSegment(good)
+    for k, v in enumerate("abc"):
+        words, cnt = g.filter_bitmap(Q.SelectorDimFilter("d", v).optimize(), Q)
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+        assert cnt == int((ids == k).sum()) and np.array_equal(bits, ids == k), v
+    g.close()
+    # the legal empty bitmap (no-run cookie, 0 containers: 8 bytes) still attaches
+    empty, _ = write("empty", small, 1, lambda data: struct.pack("<II", 12346, 0), BV.roaring_canonical)
+    g = S.GpuSegment(empty)
+    assert g.filter_bitmap(Q.SelectorDimFilter("d", "b").optimize(), Q)[1] == 0
+    assert g.filter_bitmap(Q.SelectorDimFilter("d", "a").optimize(), Q)[1] == int(a.sum())
+    g.close()
+    for corrupt, targets in ((_truncated, (0, 1)), (_offset_past_end, (1,)), (_run_count_too_large, (0,)),
+                             (_headers_overrun, (0, 1)), (_bad_cookie, (0, 1))):
+        for t in targets:
+            path, size = write(f"{corrupt.__name__}_{t}", small, t, corrupt, BV.roaring_canonical)
+            assert size <= 32768
+            must_reject(path, (corrupt.__name__, "abc"[t]))
+    # over the split size: a density-0.5 value over five containers, as run containers (run cookie with
+    # an offset header, about 330 KB) and as bitmap containers (no-run cookie, 40 KB)
+    nb = 5 * 65536
+    half = np.random.default_rng(11).random(nb) < 0.5
+    big = W.SegmentSpec(timestamps=np.arange(nb, dtype=np.int64), dims={"d": (["x", "y"], np.where(half, 0, 1).astype(np.int32))},
+                        metrics={"m": ("long", np.arange(nb) % 7)}, interval=(0, nb))
+    for encode, corruptions in ((BV.roaring_all_run, (_truncated, _offset_past_end, _run_count_too_large,
+                                                      _headers_overrun, _bad_cookie)),
+                                (BV.roaring_canonical, (_truncated, _offset_past_end, _headers_overrun))):
+        for corrupt in corruptions:
+            path, size = write(f"big_{encode.__name__}_{corrupt.__name__}", big, 0, corrupt, encode)
+            assert size > 32768
+            must_reject(path, (corrupt.__name__, encode.__name__))
 
 
 def test_corrupt_multi_value_row_lists(tmp_path, Q, W):
