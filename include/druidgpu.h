@@ -44,6 +44,14 @@
  *                               (query/scan/ScanQueryEngine.java:59-264) over the call's segments with the shared
  *                               limit of mergeRunners (ScanQueryRunnerFactory.java:64-96); the rowset is the
  *                               columnar form of the ScanResultValue batches (ScanResultValue.java)
+ *   dg_topn_run_post / dg_topn_merge_post
+ *                            <- the same two for a NumericTopNMetricSpec that names a post-aggregator:
+ *                               TopNNumericResultBuilder.addEntry (query/topn/TopNNumericResultBuilder.java:112-183)
+ *                               and TopNBinaryFn (TopNBinaryFn.java:65-71,97-110) compute it before they rank
+ *   dg_result_post_aggregate <- the post-aggregators GroupByQuery.postProcess decides on, which
+ *                               GroupByStrategyV2.mergeResults (strategy/GroupByStrategyV2.java:286-300) computes first
+ *                               (query/aggregation/post/{Arithmetic,FieldAccess,FinalizingFieldAccess,Constant,
+ *                               DoubleGreatest,DoubleLeast,LongGreatest,LongLeast}PostAggregator.java)
  *   dg_result_*              <- the merged grouper's sorted iterator (ConcurrentGrouper.iterator(true))
  *   dg_result_export / dg_keys_partition / dg_merge
  *                            <- QueryRunnerFactory.mergeRunners across devices (query/QueryRunnerFactory.java:62):
@@ -749,6 +757,96 @@ typedef struct {
   double sort_ms;   /* device time of the word loads, the sorts and the gather */
 } dg_post_info;
 int dg_result_post_process(dg_result* res, const dg_post_process* spec, dg_post_info* info /* may be NULL */);
+/* ---- post-aggregators the device decides on ----
+ * The VALUES of post-aggregators stay the caller's (the Java toolchests compute them per row:
+ * GroupByStrategyV2.mergeResults, GroupByStrategyV2.java:286-300). Two DECISIONS of GroupByQuery.postProcess depend
+ * on them: a having spec over a post-aggregator (GroupByQueryRunnerTest.testPostAggHavingSpec) and a limit spec
+ * ordered by one (DefaultLimitSpec.makeComparator takes postAgg.getComparator(), DefaultLimitSpec.java:190-260).
+ * dg_result_post_aggregate evaluates the post-aggregators those decisions need for every group of a resident
+ * result, and dg_result_post_process then reads them like aggregators.
+ *
+ * A post-aggregator is a postfix program over one group's aggregator slots, compiled and type-checked by the
+ * caller (the device never sees JSON or names). Operand types are static; the stack holds raw 64-bit words, at
+ * most DG_POST_MAX_STACK of them; a program has at most DG_POST_MAX_OPS ops and leaves exactly one value.
+ *   DG_POST_AGG arg         push aggregator `arg` of the group: long outputs push the int64, double outputs the
+ *                           double, float outputs the exactly widened float32 (FieldAccessPostAggregator.java +
+ *                           Number.doubleValue); a DG_AGG_PAIR_TIME entry cannot be read
+ *   DG_POST_CONST_D/_L imm  push a double (its bits) / a long constant (ConstantPostAggregator.java)
+ *   DG_POST_L2D             (double) long          DG_POST_D2L  Java's (long) double: NaN -> 0, saturating
+ *   DG_POST_ADD/SUB/MUL     IEEE fp64, each op rounded on its own (ArithmeticPostAggregator.java:206-228)
+ *   DG_POST_DIV             rhs == 0.0 ? 0.0 : lhs / rhs (:229-235)       DG_POST_QUOT  lhs / rhs (:236-242)
+ *   DG_POST_DMAX/DMIN       Double.compare(b, a) > 0 ? b : a / < 0 (DoubleGreatestPostAggregator.java:77-92,
+ *                           DoubleLeastPostAggregator.java); the caller folds from -inf / +inf constants
+ *   DG_POST_LMAX/LMIN       Long.compare (LongGreatestPostAggregator.java:76-93, LongLeastPostAggregator.java);
+ *                           folded from Long.MIN_VALUE / MAX_VALUE
+ * A NaN value is the canonical NaN (Double.doubleToLongBits). `order` is the comparator of the top-level
+ * post-aggregator: DG_POST_ORDER_DOUBLE (Double.compareTo: arithmetic by default, doubleGreatest / doubleLeast),
+ * DG_POST_ORDER_LONG (longGreatest / longLeast), DG_POST_ORDER_NUMERIC_FIRST (ArithmeticPostAggregator.Ordering.
+ * numericFirst, :277-299: -inf < +inf < NaN < every finite value), DG_POST_ORDER_NONE (ConstantPostAggregator's
+ * always-equal comparator: an order column of it decides nothing).
+ *
+ * dg_result_post_aggregate: a dg_groupby_run* / dg_merge / dg_groupby_merge_devices result (either grouper) gets
+ * n_cols (1..DG_POST_MAX_COLS) columns [n_cols][groups] beside its slots, one launch (k_post_eval). Refused before
+ * any launch with DG_ERR_ARG, the result unchanged: a limited or post-processed result, a second call, a program
+ * that is too long, under- or overflows the stack, mixes operand types, does not end with exactly one value or
+ * whose order kind does not fit its value's type, a slot index out of range, DG_POST_AGG of a DG_AGG_PAIR_TIME
+ * slot. *out_ms = the kernel's device time (0 without phase timing).
+ * dg_result_post_process afterwards: a DG_HAVING_AGG_RANGE.arg or DG_ORDER_AGG index n_aggs + j means post column
+ * j, its interval / order under the column's order kind (keys: LONG v ^ 2^63; DOUBLE as a double aggregator;
+ * NUMERIC_FIRST -inf -> 0, +inf -> 1, NaN -> 2, finite -> the double key; NONE: the key 0). Without post columns
+ * such an index is refused as before. The columns are dropped by dg_result_post_process: they exist to decide.
+ * dg_result_post_values: the raw words of post column `col` for groups [start, start + count), before
+ * dg_result_post_process (a shim that would rather not recompute the values reads them here). */
+#define DG_POST_MAX_OPS 64
+#define DG_POST_MAX_STACK 16
+#define DG_POST_MAX_COLS 16
+#define DG_POST_AGG 0
+#define DG_POST_CONST_D 1
+#define DG_POST_CONST_L 2
+#define DG_POST_L2D 3
+#define DG_POST_D2L 4
+#define DG_POST_ADD 5
+#define DG_POST_SUB 6
+#define DG_POST_MUL 7
+#define DG_POST_DIV 8
+#define DG_POST_QUOT 9
+#define DG_POST_DMAX 10
+#define DG_POST_DMIN 11
+#define DG_POST_LMAX 12
+#define DG_POST_LMIN 13
+#define DG_POST_ORDER_NONE 0
+#define DG_POST_ORDER_DOUBLE 1
+#define DG_POST_ORDER_LONG 2
+#define DG_POST_ORDER_NUMERIC_FIRST 3
+typedef struct {
+  int32_t op;   /* DG_POST_* */
+  int32_t arg;  /* DG_POST_AGG: index into the call's aggregators */
+  uint64_t imm; /* DG_POST_CONST_D: the double's bits; DG_POST_CONST_L: the long */
+} dg_post_agg_op;
+typedef struct {
+  const dg_post_agg_op* ops;
+  int32_t n_ops;
+  int32_t order; /* DG_POST_ORDER_* */
+} dg_post_agg;
+int dg_result_post_aggregate(dg_result* res, const dg_post_agg* cols, int32_t n_cols, double* out_ms /* may be NULL */);
+int dg_result_post_values(const dg_result* res, int32_t col, int64_t start, int64_t count, uint64_t* out);
+/* topN ranked by a post-aggregator: NumericTopNMetricSpec may name one (query/topn/NumericTopNMetricSpec.java);
+ * TopNNumericResultBuilder.addEntry (TopNNumericResultBuilder.java:112-183) computes the pruned post-aggregators per
+ * dimension value, per segment, before its priority queue, and TopNBinaryFn (TopNBinaryFn.java:65-71,97-110)
+ * recomputes them after every combine. dg_topn_run_post / dg_topn_merge_post are the _opts forms with one
+ * trailing program (metric == NULL: the _opts form itself). With a program topn->metric_agg is ignored: every
+ * touched value's ranking key is the program over the value's aggregator slots under the program's order kind
+ * (`inverted` flips it); the selection, the candidate ordering, out_cut_ties, the per-bucket lists and the merge's
+ * re-ranking after each combine are otherwise unchanged, the host steps running the same evaluator as the device.
+ * Outputs stay n_aggs slots per entry: the caller computes the values it shows (TopNQueryQueryToolChest.java:
+ * 196-206). DG_ERR_ARG before any launch: a program dg_result_post_aggregate would refuse, DG_POST_ORDER_NONE (a
+ * comparator that ranks nothing), a dimension-ordered spec (topn->dim_order >= 0) with a program. */
+int dg_topn_run_post(dg_segment* const* segs, int32_t n_segs, const dg_scan* scan, const dg_topn* topn,
+                     const dg_topn_opts* opts, const dg_post_agg* metric, int32_t* out_n, int32_t* out_ids,
+                     uint64_t* out_values, dg_metrics* metrics);
+int dg_topn_merge_post(dg_segment* const* segs, const dg_scan* scan, const dg_topn* topn, const dg_topn_lists* in,
+                       const dg_topn_opts* opts, const dg_post_agg* metric, int32_t* out_n, int32_t* out_list,
+                       int64_t* out_keys, uint64_t* out_values);
 /* number of merged groups */
 int64_t dg_result_groups(const dg_result* res);
 /* groups [start, start + count), in result order (bucket time, then dimension values in Java

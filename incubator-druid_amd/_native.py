@@ -194,6 +194,29 @@ class dg_post_info(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# dg_result_post_aggregate: post-aggregator programs (the op codes are query.POST_*)
+POST_MAX_OPS, POST_MAX_STACK, POST_MAX_COLS = 64, 16, 16
+
+
+class dg_post_agg_op(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("imm", ctypes.c_uint64)]
+
+
+class dg_post_agg(ctypes.Structure):
+    _fields_ = [("ops", ctypes.c_void_p), ("n_ops", ctypes.c_int32), ("order", ctypes.c_int32)]
+
+
+def make_post_aggs(programs):
+    """[(ops [(op, arg, imm)], order)] -> (dg_post_agg array, keep-alive list)."""
+    keep, cols = [], []
+    for ops, order in programs:
+        arr = (dg_post_agg_op * max(len(ops), 1))(*[dg_post_agg_op(int(o), int(a), int(i) & ((1 << 64) - 1))
+                                                    for o, a, i in ops])
+        keep.append(arr)
+        cols.append(dg_post_agg(ctypes.cast(arr, ctypes.c_void_p), len(ops), int(order)))
+    return (dg_post_agg * max(len(cols), 1))(*cols), keep
+
+
 class dg_keyspace(ctypes.Structure):
     _fields_ = [("n_dims", ctypes.c_int32), ("card", ctypes.c_void_p), ("period_ms", ctypes.c_int64),
                 ("bucket0", ctypes.c_int64), ("n_buckets", ctypes.c_int64), ("universal_time", ctypes.c_int64),
@@ -218,7 +241,8 @@ EXPORTS = [
     "dg_debug_groupby_sort_plan",
     "dg_groupby_run_dims", "dg_result_dim_type", "dg_result_dim_longs", "dg_debug_long_dim_info",
     "dg_topn_run_opts", "dg_topn_merge_opts", "dg_segment_numeric_dim_values", "dg_segment_numeric_dim_info",
-    "dg_result_post_process",
+    "dg_result_post_process", "dg_result_post_aggregate", "dg_result_post_values",
+    "dg_topn_run_post", "dg_topn_merge_post",
 ]
 
 _lib = None
@@ -288,6 +312,8 @@ def lib():
         "dg_result_release": (None, [vp]),
         "dg_result_limit": (ctypes.c_int, [vp, P(dg_limit)]),
         "dg_result_post_process": (ctypes.c_int, [vp, P(dg_post_process), P(dg_post_info)]),
+        "dg_result_post_aggregate": (ctypes.c_int, [vp, P(dg_post_agg), i32, P(ctypes.c_double)]),
+        "dg_result_post_values": (ctypes.c_int, [vp, i32, i64, i64, vp]),
         "dg_keyspace_bits": (ctypes.c_int, [P(dg_keyspace), P(i32)]),
         "dg_result_export": (ctypes.c_int, [vp, P(dg_keyspace), P(vp), vp, vp]),
         "dg_keys_partition": (ctypes.c_int, [vp, vp, i64, vp, i32, vp]),
@@ -313,6 +339,10 @@ def lib():
                                             P(dg_metrics)]),
         "dg_topn_merge_opts": (ctypes.c_int, [vp, P(dg_scan), P(dg_topn), P(dg_topn_lists), P(dg_topn_opts), P(i32),
                                               vp, vp, vp]),
+        "dg_topn_run_post": (ctypes.c_int, [P(vp), i32, P(dg_scan), P(dg_topn), P(dg_topn_opts), P(dg_post_agg), vp, vp,
+                                            vp, P(dg_metrics)]),
+        "dg_topn_merge_post": (ctypes.c_int, [vp, P(dg_scan), P(dg_topn), P(dg_topn_lists), P(dg_topn_opts),
+                                              P(dg_post_agg), P(i32), vp, vp, vp]),
         "dg_segment_numeric_dim_values": (ctypes.c_int, [vp, cp, vp, i32, vp]),
         "dg_segment_numeric_dim_info": (ctypes.c_int, [vp, cp, P(i32), P(i64), P(i64), P(ctypes.c_double)]),
     }

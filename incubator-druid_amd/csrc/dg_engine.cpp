@@ -26,6 +26,17 @@
 
 #include "dg_internal.h"
 
+static_assert(DG_POST_AGG == dg::PA_AGG && DG_POST_CONST_D == dg::PA_CONST_D && DG_POST_CONST_L == dg::PA_CONST_L &&
+                  DG_POST_L2D == dg::PA_L2D && DG_POST_D2L == dg::PA_D2L && DG_POST_ADD == dg::PA_ADD &&
+                  DG_POST_SUB == dg::PA_SUB && DG_POST_MUL == dg::PA_MUL && DG_POST_DIV == dg::PA_DIV &&
+                  DG_POST_QUOT == dg::PA_QUOT && DG_POST_DMAX == dg::PA_DMAX && DG_POST_DMIN == dg::PA_DMIN &&
+                  DG_POST_LMAX == dg::PA_LMAX && DG_POST_LMIN == dg::PA_LMIN,
+              "the ABI's op codes are the evaluator's");
+static_assert(DG_POST_ORDER_NONE == dg::PA_ORDER_NONE && DG_POST_ORDER_DOUBLE == dg::PA_ORDER_DOUBLE &&
+                  DG_POST_ORDER_LONG == dg::PA_ORDER_LONG && DG_POST_ORDER_NUMERIC_FIRST == dg::PA_ORDER_NUMERIC_FIRST &&
+                  DG_POST_MAX_OPS == dg::kPostAggMaxOps && DG_POST_MAX_STACK == dg::kPostAggMaxStack,
+              "the ABI's order kinds and limits are the evaluator's");
+
 namespace dg {
 
 // ------------------------------------------------------------------------------------------------
@@ -3087,6 +3098,77 @@ int dg_timeseries_run(dg_segment* const* segs, int32_t n, const dg_scan* q, int3
 }
 
 // ------------------------------------------------------------------------------------------------
+// post-aggregator programs (dg_postagg.h): the ABI form checked into the evaluator's
+// ------------------------------------------------------------------------------------------------
+// the PA_SLOT_* class of every aggregator slot, -1 for a slot no program may read (a DG_AGG_PAIR_TIME entry:
+// half of a pair, not a Number of the row). okind: output-side kinds (FlPlan::okind / dg_result::kinds).
+static void post_slot_classes(const int32_t* okind, const int32_t* abi_kind, int n, int8_t* cls) {
+  for (int a = 0; a < n; ++a) {
+    switch (okind[a]) {
+      case DG_AGG_COUNT:
+      case DG_AGG_LONG_SUM:
+      case DG_AGG_LONG_MIN:
+      case DG_AGG_LONG_MAX: cls[a] = PA_SLOT_LONG; break;
+      case DG_AGG_DOUBLE_SUM:
+      case DG_AGG_DOUBLE_MIN:
+      case DG_AGG_DOUBLE_MAX: cls[a] = PA_SLOT_DOUBLE; break;
+      case DG_AGG_FLOAT_SUM:
+      case DG_AGG_FLOAT_MIN:
+      case DG_AGG_FLOAT_MAX: cls[a] = PA_SLOT_FLOAT; break;
+      default: cls[a] = -1;
+    }
+    if (abi_kind && abi_kind[a] == DG_AGG_PAIR_TIME) cls[a] = -1;
+  }
+}
+
+// dg_post_agg -> a checked PostAggProg over n slots of classes cls; DG_ERR_ARG naming program `c` otherwise
+static int post_prog_build(const dg_post_agg& in, const int8_t* cls, int n, int c, PostAggProg* out) {
+  PostAggProg& p = *out;
+  memset(&p, 0, sizeof p);
+  if (in.n_ops < 1 || in.n_ops > DG_POST_MAX_OPS || !in.ops)
+    return set_error(DG_ERR_ARG, "post-aggregator %d: %d ops (1..%d)", c, in.n_ops, DG_POST_MAX_OPS);
+  p.n = in.n_ops;
+  p.order = in.order;
+  for (int i = 0; i < in.n_ops; ++i) {
+    const dg_post_agg_op& o = in.ops[i];
+    if (o.op < 0 || o.op >= PA_N_OPS) return set_error(DG_ERR_ARG, "post-aggregator %d op %d: unknown op %d", c, i, o.op);
+    p.op[i] = (int8_t)o.op;
+    p.imm[i] = o.imm;
+    if (o.op == DG_POST_AGG) {
+      if (o.arg < 0 || o.arg >= n) return set_error(DG_ERR_ARG, "post-aggregator %d op %d: aggregator %d of %d", c, i, o.arg, n);
+      if (cls[o.arg] < 0)
+        return set_error(DG_ERR_ARG, "post-aggregator %d op %d: aggregator %d is a DG_AGG_PAIR_TIME entry", c, i, o.arg);
+      p.arg[i] = (int16_t)o.arg;
+      p.cls[i] = cls[o.arg];
+    }
+  }
+  static const char* const why[] = {"", "length", "unknown op", "slot index", "stack underflow", "stack overflow",
+                                    "operand type", "does not end with exactly one value", "order kind"};
+  const int rc = pa_check(p, cls, n, nullptr);
+  if (rc) return set_error(DG_ERR_ARG, "post-aggregator %d: %s", c, why[-rc]);
+  return DG_OK;
+}
+
+// the ranking key of a topN metric program over ABI-encoded slots (what the device's metric_prog_key computes)
+static uint64_t prog_metric_key(const PostAggProg& p, const uint64_t* abi_slots, int inverted) {
+  const uint64_t k = pa_order_key(p.order, pa_eval(p, [&](int s) { return abi_slots[s]; }));
+  return inverted ? ~k : k;
+}
+
+// a dg_topn_*_post metric program checked against the call's aggregators
+static int topn_metric_prog(const dg_post_agg* metric, const dg_topn* t, const FlPlan& fl, int na, TopnMetricProg* out) {
+  if (t->dim_order >= 0) return set_error(DG_ERR_ARG, "a dimension-ordered topN takes no metric program");
+  int8_t cls[kMaxAggs];
+  post_slot_classes(fl.okind, fl.abi_kind, na, cls);
+  memset(out, 0, sizeof *out);
+  const int rc = post_prog_build(*metric, cls, na, 0, &out->p);
+  if (rc) return rc;
+  if (out->p.order == DG_POST_ORDER_NONE) return set_error(DG_ERR_ARG, "a topN cannot rank on an always-equal comparator");
+  for (int a = 0; a < na; ++a) out->okind[a] = fl.okind[a];
+  return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // topN
 // ------------------------------------------------------------------------------------------------
 static uint64_t metric_key_host(uint64_t slot, int kind, int inverted) {
@@ -3164,7 +3246,7 @@ static int numeric_dim_orders(Column* c, bool text, int slot) {
 // decimal text (Column::nd_text). The reference offers the values in its hash map's iteration order, so
 // which values tied with the K-th metric it keeps is arbitrary: out_cut_ties reports how many were left out.
 static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, const dg_topn_opts* opts,
-                         int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics) {
+                         const dg_post_agg* metric, int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics) {
   auto t0 = std::chrono::steady_clock::now();
   HostTrace ht;
   Context* ctx;
@@ -3182,12 +3264,15 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
   if (q->period_ms && !t->out_bucket_time) return set_error(DG_ERR_ARG, "out_bucket_time");
   const bool dim = t->dim_order >= 0;
   if (dim && t->dim_order >= kOrderSlots) return set_error(DG_ERR_ARG, "order slot %d", t->dim_order);
-  if (!dim && (t->metric_agg < 0 || t->metric_agg >= q->n_aggs)) return set_error(DG_ERR_ARG, "metric index");
+  if (!dim && !metric && (t->metric_agg < 0 || t->metric_agg >= q->n_aggs)) return set_error(DG_ERR_ARG, "metric index");
   if (t->threshold <= 0) return set_error(DG_ERR_ARG, "threshold");
   AggPlan plan;
   FlPlan fl;
   rc = make_plan(q, &plan, &fl);
   if (rc) return rc;
+  // a topN ranked by a post-aggregator: the program, checked before anything is launched
+  TopnMetricProg mprog;
+  if (metric && (rc = topn_metric_prog(metric, t, fl, plan.n, &mprog))) return rc;
   qs.aggs = fl.aggs;  // (the engine's aggregators: first/last pairs as their internal min / max slots)
   FlCall flc;
   flc.fl = &fl;
@@ -3458,9 +3543,16 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
   // selection + gather of the candidates' records, all segments in one launch (staged before the
   // decode: its upload carries the bins', the scan's and the selection's tables)
   // (a first/last metric: its slot holds the pair's value when the selection runs, k_fl_resolve)
-  const int mk = dim ? DG_AGG_COUNT : fl.okind[t->metric_agg];
-  const int metric_agg = dim ? 0 : t->metric_agg;
+  const int mk = dim || metric ? DG_AGG_COUNT : fl.okind[t->metric_agg];
+  const int metric_agg = dim || metric ? 0 : t->metric_agg;
   const int metric_op = (slot_op(mk) << 8) | mk;
+  // the host's key of a record's slots (device encoding), the same evaluator over the finalized slots
+  auto host_key = [&](const uint64_t* slots) {
+    if (!metric) return metric_key_host(slots[metric_agg], mk, t->inverted);
+    uint64_t abi[kMaxAggs];
+    for (int a = 0; a < plan.n; ++a) abi[a] = finalize_slot(fl.okind[a], slots[a]);
+    return prog_metric_key(mprog.p, abi, t->inverted);
+  };
   std::vector<TopnSelJob> sel;
   std::vector<int> sel_seg, sel_bucket;  // one selection per (segment, bucket)
   std::vector<int64_t> jgcap, jgoff, out_base;
@@ -3646,9 +3738,17 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     if (rc) return rc;
   }
   flc.resolve(st);  // before the selection chain: a first/last aggregator may be the ordering metric
+  const TopnMetricProg* d_mprog = nullptr;
+  if (ns && metric) {
+    TopnMetricProg* dp;
+    TopnMetricProg* hp = up_take<TopnMetricProg>(cs, 1, &dp, st);
+    if (!hp) return set_error(DG_ERR_OOM, "topN metric program");
+    *hp = mprog;
+    d_mprog = dp;
+  }
   if (ns) {
     DG_FLUSH(cs, st);
-    launch_topn_select(d_sel, ns, max_card, na, metric_agg, metric_op, t->inverted, sel_threshold, st);
+    launch_topn_select(d_sel, ns, max_card, na, metric_agg, metric_op, t->inverted, sel_threshold, d_mprog, st);
     ht.mark("select_launched");
   }
   phase_event(ctx->ev[4], st);
@@ -3818,7 +3918,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
       // order; keep every key > kth and, of the kth ties, those the builder's queue keeps (see
       // below), already in output order
       const uint16_t* ord = order_of(k);
-      auto key_at = [&](int e) { return metric_key_host(sorted_at(k, e)[2 + t->metric_agg], mk, t->inverted); };
+      auto key_at = [&](int e) { return host_key(sorted_at(k, e) + 2); };
       const int r = std::min(nc, K) - 1;
       const uint64_t kth = key_at(r);
       bool exact = key_at(nc - 1) >= kth;  // nothing below the K-th key
@@ -3851,7 +3951,7 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
     std::vector<E> all(nc);
     for (int c = 0; c < nc; ++c) {
       const int32_t id = h_cand[k][c];
-      all[c] = E{metric_key_host(h_tab[k][(size_t)c * rec + 1 + t->metric_agg], mk, t->inverted), id, c, trank ? trank[id] : id};
+      all[c] = E{host_key(h_tab[k] + (size_t)c * rec + 1), id, c, trank ? trank[id] : id};
     }
     // (String output of a LONG column: offered in the decimal text's order; the candidates are few)
     if (trank) std::sort(all.begin(), all.end(), [](const E& a, const E& b) { return a.ord < b.ord; });
@@ -3930,12 +4030,18 @@ static int topn_run_impl(dg_segment* const* segs, int32_t n, const dg_scan* q, c
 
 int dg_topn_run(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, int32_t* out_n, int32_t* out_ids,
                 uint64_t* out_values, dg_metrics* metrics) {
-  return topn_run_impl(segs, n, q, t, nullptr, out_n, out_ids, out_values, metrics);
+  return topn_run_impl(segs, n, q, t, nullptr, nullptr, out_n, out_ids, out_values, metrics);
 }
 
 int dg_topn_run_opts(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, const dg_topn_opts* opts,
                      int32_t* out_n, int32_t* out_ids, uint64_t* out_values, dg_metrics* metrics) {
-  return topn_run_impl(segs, n, q, t, opts, out_n, out_ids, out_values, metrics);
+  return topn_run_impl(segs, n, q, t, opts, nullptr, out_n, out_ids, out_values, metrics);
+}
+
+int dg_topn_run_post(dg_segment* const* segs, int32_t n, const dg_scan* q, const dg_topn* t, const dg_topn_opts* opts,
+                     const dg_post_agg* metric, int32_t* out_n, int32_t* out_ids, uint64_t* out_values,
+                     dg_metrics* metrics) {
+  return topn_run_impl(segs, n, q, t, opts, metric, out_n, out_ids, out_values, metrics);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4326,7 +4432,7 @@ extern "C" {
 // builder breaks metric ties by the output type's compareTo: ascending keys, or for a LONG column with
 // output type STRING the decimal text's String.compareTo (long_text_key).
 static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in,
-                           const dg_topn_opts* opts, int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
+                           const dg_topn_opts* opts, const dg_post_agg* metric, int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
   if (!q || !t || !in || !out_n || (in->n_lists > 0 && (!in->list_n || !in->keys || !in->values)))
     return set_error(DG_ERR_ARG, "null argument");
   const int32_t out_type = opts && opts->output_type ? opts->output_type : DG_COL_STRING;
@@ -4336,9 +4442,13 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
   FlPlan fl;
   int rc = make_plan(q, &plan, &fl);
   if (rc) return rc;
-  if (t->metric_agg < 0 || t->metric_agg >= plan.n) return set_error(DG_ERR_ARG, "metric index");
+  if (!metric && (t->metric_agg < 0 || t->metric_agg >= plan.n)) return set_error(DG_ERR_ARG, "metric index");
   if (t->threshold <= 0) return set_error(DG_ERR_ARG, "threshold");
-  const int na = plan.n, mk = fl.okind[t->metric_agg], nl = in->n_lists;
+  // TopNBinaryFn recomputes the pruned post-aggregators after every combine (TopNBinaryFn.java:65-71,97-110) and
+  // the builder ranks on them: the same evaluator over the entries' ABI slots
+  TopnMetricProg mprog;
+  if (metric && (rc = topn_metric_prog(metric, t, fl, plan.n, &mprog))) return rc;
+  const int na = plan.n, mk = metric ? DG_AGG_COUNT : fl.okind[t->metric_agg], nl = in->n_lists;
   // the dimension column of every list's segment, resolved once (segment mode)
   std::vector<const Column*> lcol(nl > 0 ? nl : 1, nullptr);
   int num_type = 0;  // segment mode: DG_COL_* of a numeric dimension
@@ -4465,7 +4575,8 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
   };
   std::vector<Ent> acc, cur;
   bool have = false;
-  const int ma = t->metric_agg, inv = t->inverted;
+  const int ma = metric ? 0 : t->metric_agg, inv = t->inverted;
+  auto entry_key = [&](const uint64_t* v) { return metric ? prog_metric_key(mprog.p, v, inv) : abi_metric_key(mk, v[ma], inv); };
   for (int l = 0; l < nl; ++l) {
     const int cnt = in->list_n[l];
     if (cnt < 0) continue;  // no cursor: no result from this segment
@@ -4474,7 +4585,7 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
     const uint64_t* vs = in->values + (int64_t)l * in->stride * na;
     for (int e = 0; e < cnt; ++e) {  // the entries reference the caller's rows (no copy)
       const uint64_t* v = vs + (int64_t)e * na;
-      cur[e] = Ent{l, ks[e], abi_metric_key(mk, v[ma], inv), 0, v};
+      cur[e] = Ent{l, ks[e], entry_key(v), 0, v};
     }
     // the value hashes in a pass of their own: independent dictionary reads the core overlaps (one
     // random read per entry; interleaved with the table probes they were serialized)
@@ -4509,7 +4620,7 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
         }
         uint64_t* w = const_cast<uint64_t*>(a.v);
         combine_abi_row(plan, fl, w, e.v);
-        a.mkey = abi_metric_key(mk, w[ma], inv);
+        a.mkey = entry_key(w);
       } else {
         acc.push_back(e);
       }
@@ -4528,12 +4639,18 @@ static int topn_merge_impl(dg_segment* const* segs, const dg_scan* q, const dg_t
 
 int dg_topn_merge(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in, int32_t* out_n,
                   int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
-  return topn_merge_impl(segs, q, t, in, nullptr, out_n, out_list, out_keys, out_values);
+  return topn_merge_impl(segs, q, t, in, nullptr, nullptr, out_n, out_list, out_keys, out_values);
 }
 
 int dg_topn_merge_opts(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in,
                        const dg_topn_opts* opts, int32_t* out_n, int32_t* out_list, int64_t* out_keys, uint64_t* out_values) {
-  return topn_merge_impl(segs, q, t, in, opts, out_n, out_list, out_keys, out_values);
+  return topn_merge_impl(segs, q, t, in, opts, nullptr, out_n, out_list, out_keys, out_values);
+}
+
+int dg_topn_merge_post(dg_segment* const* segs, const dg_scan* q, const dg_topn* t, const dg_topn_lists* in,
+                       const dg_topn_opts* opts, const dg_post_agg* metric, int32_t* out_n, int32_t* out_list,
+                       int64_t* out_keys, uint64_t* out_values) {
+  return topn_merge_impl(segs, q, t, in, opts, metric, out_n, out_list, out_keys, out_values);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4914,12 +5031,16 @@ struct dg_result {
   std::vector<int32_t> abi_kinds;                     // the caller's kinds when they differ (first/last pairs:
                                                       // `kinds` then has the value's type; such a result is not merged)
   dg_grouper_info grouper{};                          // what grouped it (dg_result_grouper_info)
+  uint64_t* post = nullptr;                           // [post_order.size()][cap] post-aggregator columns
+  std::vector<int32_t> post_order;                    // (dg_result_post_aggregate): DG_POST_ORDER_* of each
+  bool post_done = false;                             // dg_result_post_aggregate ran (its columns may be dropped since)
   ~dg_result() {
     if (!ctx) return;
     std::lock_guard<std::mutex> g(ctx->mu);
     hipSetDevice(ctx->device);
     dg::result_free(ctx, keys);
     dg::result_free(ctx, slots);
+    dg::result_free(ctx, post);
   }
 };
 
@@ -4931,6 +5052,7 @@ struct ResultDrop {
     if (r->ctx) {
       dg::result_free(r->ctx, r->keys);
       dg::result_free(r->ctx, r->slots);
+      dg::result_free(r->ctx, r->post);
     }
     r->ctx = nullptr;
     delete r;
@@ -5903,6 +6025,7 @@ int dg_result_dim_dictionary(const dg_result* r, int32_t dim, int64_t* offsets, 
 int dg_result_limit(dg_result* r, const dg_limit* spec) {
   if (!r || !spec || spec->limit <= 0 || spec->n_columns < 0 || (spec->n_columns > 0 && !spec->columns))
     return set_error(DG_ERR_ARG, "bad limit spec");
+  if (r->post) return set_error(DG_ERR_ARG, "the result has post-aggregator columns (dg_result_post_process reads them)");
   Context* ctx = r->ctx;
   const KeyLayout& lay = r->lay;
   // the push-down field order: time, ORDER BY dimensions (first mention), the other dimensions
@@ -6026,6 +6149,7 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
   if ((int)r->kinds.size() != r->naggs) return set_error(DG_ERR_ARG, "the result does not know its aggregators");
   Context* ctx = r->ctx;
   const KeyLayout& lay = r->lay;
+  const int npost = r->post ? (int)r->post_order.size() : 0;
   // ---- the having program: indices and stack discipline ----
   PostHaving hp;
   memset(&hp, 0, sizeof hp);
@@ -6049,9 +6173,15 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
         if (depth < 1) return set_error(DG_ERR_ARG, "having op %d: NOT of an empty stack", i);
         break;
       case DG_HAVING_AGG_RANGE:
-        if (h.arg < 0 || h.arg >= r->naggs) return set_error(DG_ERR_ARG, "having op %d: aggregator %d of %d", i, h.arg, r->naggs);
-        hp.arg[i] = 1 + h.arg;
-        hp.kind[i] = r->kinds[h.arg];
+        if (h.arg < 0 || h.arg >= r->naggs + npost)
+          return set_error(DG_ERR_ARG, "having op %d: aggregator %d of %d (+ %d post columns)", i, h.arg, r->naggs, npost);
+        if (h.arg >= r->naggs) {  // post column j under its order kind
+          hp.arg[i] = h.arg - r->naggs;
+          hp.kind[i] = kPostColKind + r->post_order[h.arg - r->naggs];
+        } else {
+          hp.arg[i] = 1 + h.arg;
+          hp.kind[i] = r->kinds[h.arg];
+        }
         ++depth;
         break;
       case DG_HAVING_DIM_EQ:
@@ -6089,7 +6219,7 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
   const bool timed = lay.bucket_bits > 0;
   const bool time_last = timed && spec->sort_by_dims_first != 0;
   if (timed && !time_last) key_field(-1, 0, nullptr);
-  std::vector<bool> dim_used(r->ndims, false), agg_used(r->naggs, false);
+  std::vector<bool> dim_used(r->ndims, false), agg_used(r->naggs + npost, false);
   for (int c = 0; c < spec->n_columns; ++c) {
     const dg_post_column& oc = spec->columns[c];
     if (oc.kind == DG_ORDER_DIM) {
@@ -6106,11 +6236,23 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
       dim_used[oc.index] = true;
       key_field(oc.index, oc.descending != 0, oc.rank);
     } else if (oc.kind == DG_ORDER_AGG) {
-      if (oc.index < 0 || oc.index >= r->naggs) return set_error(DG_ERR_ARG, "ORDER BY aggregator %d of %d", oc.index, r->naggs);
+      if (oc.index < 0 || oc.index >= r->naggs + npost)
+        return set_error(DG_ERR_ARG, "ORDER BY aggregator %d of %d (+ %d post columns)", oc.index, r->naggs, npost);
       if (agg_used[oc.index]) continue;
       agg_used[oc.index] = true;
       Field x;
       memset(&x, 0, sizeof x);
+      if (oc.index >= r->naggs) {  // post column j under its order kind; an always-equal comparator decides nothing
+        const int j = oc.index - r->naggs;
+        if (r->post_order[j] == DG_POST_ORDER_NONE) continue;
+        x.f.type = POST_F_AGG64;
+        x.f.bits = 64;
+        x.f.desc = oc.descending != 0;
+        x.f.slot = j;
+        x.f.kind = kPostColKind + r->post_order[j];
+        chain.push_back(x);
+        continue;
+      }
       const int k = r->kinds[oc.index];
       const bool f32 = k == DG_AGG_FLOAT_SUM || k == DG_AGG_FLOAT_MIN || k == DG_AGG_FLOAT_MAX;
       x.f.type = f32 ? POST_F_AGG32 : POST_F_AGG64;
@@ -6137,6 +6279,12 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
   pi.groups_in = pi.groups_after_having = n;
   pi.groups_kept = m;
   if (n == 0 || (!having && !sort)) {  // LimitingFn over the natural order: the first groups are the answer
+    if (r->post) {
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      hipSetDevice(ctx->device);
+      result_free(ctx, r->post);
+      r->post = nullptr;
+    }
     r->ngroups = m;
     r->limited = true;
     if (info) *info = pi;
@@ -6218,7 +6366,7 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
         drop();
         return set_error(DG_ERR_DEVICE, "hipMemsetAsync of the references");
       }
-    launch_post_having(r->keys, r->slots, r->cap, n, hp, sel, st);
+    launch_post_having(r->keys, r->slots, r->cap, n, hp, r->post, sel, st);
     launch_rows_select(sel, n, (uint64_t)(sort ? n : m), tile_cnt, d_info, sb.refs[0], st);
     cs->late.push_back({h_info, d_info, 32});
   }
@@ -6227,7 +6375,8 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
     const bool first = w == (int)words.size() - 1;
     const uint32_t* refs_in = first ? (having ? sb.refs[0] : nullptr) : sb.refs[sb.cur];
     uint32_t* refs_out = first && !having ? sb.refs[sb.cur] : nullptr;  // (survivors already lie in refs[0] = refs[cur])
-    launch_post_sort_word(r->keys, r->slots, r->cap, n, d_info, refs_in, words[w], sb.keys[sb.cur], refs_out, sb.n, st);
+    launch_post_sort_word(r->keys, r->slots, r->cap, n, d_info, refs_in, words[w], r->post, sb.keys[sb.cur], refs_out,
+                          sb.n, st);
     launch_radix_sort(&sb, words[w].bits, st);
   }
   launch_limit_gather(&sb, m, r->keys, r->slots, r->cap, rec, nk, ns, std::max<int64_t>(m, 1), st);
@@ -6248,6 +6397,8 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
   }
   result_free(ctx, r->keys);
   result_free(ctx, r->slots);
+  result_free(ctx, r->post);  // the post columns existed to decide
+  r->post = nullptr;
   r->keys = nk;
   r->slots = ns;
   r->cap = std::max<int64_t>(m, 1);
@@ -6255,6 +6406,59 @@ int dg_result_post_process(dg_result* r, const dg_post_process* spec, dg_post_in
   r->limited = true;
   if (info) *info = pi;
   return DG_OK;
+}
+
+// Post-aggregator columns of a resident result (the header's comment): the programs checked on the host
+// (pa_check of dg_postagg.h, the evaluator the kernel runs), uploaded, one k_post_eval launch.
+int dg_result_post_aggregate(dg_result* r, const dg_post_agg* cols, int32_t n_cols, double* out_ms) {
+  if (out_ms) *out_ms = 0.0;
+  if (!r || !cols || n_cols < 1 || n_cols > DG_POST_MAX_COLS) return set_error(DG_ERR_ARG, "bad post-aggregator columns");
+  if (r->limited) return set_error(DG_ERR_ARG, "the result is limited or post-processed already");
+  if (r->post_done) return set_error(DG_ERR_ARG, "the result has post-aggregator columns already");
+  if ((int)r->kinds.size() != r->naggs) return set_error(DG_ERR_ARG, "the result does not know its aggregators");
+  int8_t cls[kMaxAggs];
+  post_slot_classes(r->kinds.data(), (int)r->abi_kinds.size() == r->naggs ? r->abi_kinds.data() : nullptr, r->naggs, cls);
+  std::vector<PostAggProg> progs((size_t)n_cols);
+  for (int c = 0; c < n_cols; ++c)
+    if (int rc = post_prog_build(cols[c], cls, r->naggs, c, &progs[c])) return rc;
+  Context* ctx = r->ctx;
+  const int64_t n = r->ngroups;
+  CallGuard g(ctx);
+  CallScratch* cs = g.cs;
+  hipStream_t st = ctx->stream;
+  PostAggProg* d_progs = nullptr;
+  PostAggProg* h = up_take<PostAggProg>(cs, (size_t)n_cols, &d_progs, st);
+  if (!h) return set_error(DG_ERR_OOM, "post-aggregator programs");
+  memcpy(h, progs.data(), sizeof(PostAggProg) * (size_t)n_cols);
+  DG_FLUSH(cs, st);
+  uint64_t* col = static_cast<uint64_t*>(result_alloc(ctx, (size_t)std::max<int64_t>(r->cap, 1) * n_cols * 8));
+  if (!col) return set_error(DG_ERR_OOM, "%d post-aggregator columns of %lld groups", n_cols, (long long)n);
+  phase_event(ctx->ev[0], st);
+  launch_post_eval(r->slots, r->cap, n, d_progs, n_cols, col, st);
+  phase_event(ctx->ev[1], st);
+  const int rc = finish_call(cs, st);
+  if (rc) {
+    result_free(ctx, col);
+    return rc;
+  }
+  float ms = 0.f;
+  (void)phase_elapsed(&ms, ctx->ev[0], ctx->ev[1]);
+  if (out_ms) *out_ms = ms;
+  r->post = col;
+  r->post_order.resize((size_t)n_cols);
+  for (int c = 0; c < n_cols; ++c) r->post_order[c] = cols[c].order;
+  r->post_done = true;
+  return DG_OK;
+}
+
+int dg_result_post_values(const dg_result* r, int32_t col, int64_t start, int64_t count, uint64_t* out) {
+  if (!r || !r->post) return set_error(DG_ERR_ARG, "the result has no post-aggregator columns");
+  if (col < 0 || col >= (int)r->post_order.size()) return set_error(DG_ERR_ARG, "post column %d of %d", col, (int)r->post_order.size());
+  if (!out || start < 0 || count < 0 || start + count > r->ngroups) return set_error(DG_ERR_ARG, "bad result range");
+  if (count == 0) return DG_OK;
+  CallGuard g(r->ctx);
+  DG_HIP(hipMemcpyAsync(out, r->post + (size_t)col * r->cap + start, (size_t)count * 8, hipMemcpyDeviceToHost, r->ctx->stream));
+  return finish_call(g.cs, r->ctx->stream);
 }
 
 int32_t dg_result_dim_cardinality(const dg_result* r, int32_t dim) {

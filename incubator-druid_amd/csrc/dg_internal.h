@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/druidgpu.h"
+#include "dg_postagg.h"
 
 namespace dg {
 
@@ -878,8 +879,15 @@ struct TopnSelJob {
 };
 constexpr int kSelBlock = 1024;
 constexpr int kTopnOrderCap = 4096;  // k_topn_order sorts at most this many candidates
+// A topN ranked by a post-aggregator (dg_topn_run_post): the checked program and the output-side kind of every
+// slot of a record (device encoding -> finalize_dev -> the ABI slot the program reads).
+struct TopnMetricProg {
+  PostAggProg p;
+  int32_t okind[kMaxAggs];
+};
+// d_prog (device memory; NULL = the aggregator `metric`): the keys are the program's order keys instead
 void launch_topn_select(const TopnSelJob* d_jobs, int njobs, int64_t max_card, int naggs, int metric, int metric_op,
-                        int inverted, int threshold, hipStream_t s);
+                        int inverted, int threshold, const TopnMetricProg* d_prog, hipStream_t s);
 
 constexpr int kTileRows = 2048;
 
@@ -1101,8 +1109,9 @@ struct PostHaving {
   uint64_t hi[kPostMaxOps];
 };
 // sel[ceil(n / 32) + 2]: bit g = the program accepts group g (bits at or past n clear)
+// (post: the result's post-aggregator columns [n_cols][cap], read by AGG_RANGE ops of kind >= kPostColKind)
 void launch_post_having(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n, const PostHaving& p,
-                        uint32_t* sel, hipStream_t s);
+                        const uint64_t* post, uint32_t* sel, hipStream_t s);
 // One sort word: fields most significant first, each a key field (bucket / dimension id, through its
 // rank table if any), an aggregator's 64-bit order key or a float aggregator's 32-bit one;
 // a descending field is complemented within its bits.
@@ -1127,8 +1136,14 @@ struct PostWord {
 // kout[i] = word w of group g = refs_in ? refs_in[i] : i, for i < count (count = info ? info[1] : n);
 // refs_out (if given) [i] = g; n_out[0] = count
 void launch_post_sort_word(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n,
-                           const unsigned long long* info, const uint32_t* refs_in, const PostWord& w, uint64_t* kout,
-                           uint32_t* refs_out, uint32_t* n_out, hipStream_t s);
+                           const unsigned long long* info, const uint32_t* refs_in, const PostWord& w,
+                           const uint64_t* post, uint64_t* kout, uint32_t* refs_out, uint32_t* n_out, hipStream_t s);
+// Post-aggregator columns (dg_result_post_aggregate): out[c][g] = program c over group g's slots, g < n;
+// d_progs: ncols checked programs in device memory. A field / having kind of kPostColKind + PA_ORDER_* names a
+// post column in place of an aggregator slot.
+constexpr int kPostColKind = 64;
+void launch_post_eval(const uint64_t* slots, int64_t cap, int64_t n, const PostAggProg* d_progs, int ncols, uint64_t* out,
+                      hipStream_t s);
 // one record per run of the sorted merge input, partial values combined in order (device encoding,
 // SoA slots [rec][cap])
 void launch_merge_reduce(SortBufs* sb, const uint32_t* head_pos, const uint64_t* in_slots, AggPlan plan, int64_t cap,

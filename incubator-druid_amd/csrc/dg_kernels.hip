@@ -1273,6 +1273,17 @@ __device__ __forceinline__ uint64_t metric_key(uint64_t slot, int op, int kind, 
   return inverted ? ~k : k;
 }
 
+// The key of a record under a post-aggregator program (a topN ranked by a post-aggregator,
+// TopNNumericResultBuilder.java:112-183 computes it per dimension value before the priority queue): the program
+// over the record's slots as the ABI encodes them, under the program's order kind. slots = the record's first
+// aggregate slot (device encoding).
+__device__ __forceinline__ uint64_t metric_prog_key(const TopnMetricProg& mp, const uint64_t* __restrict__ slots,
+                                                    int inverted) {
+  const uint64_t v = pa_eval(mp.p, [&](int s) { return finalize_dev(mp.okind[s], slots[s]); });
+  const uint64_t k = pa_order_key(mp.p.order, v);
+  return inverted ? ~k : k;
+}
+
 // One level of the radix digit choice from its histogram (wave-parallel: 64 lanes x 4 bins, descending
 // digit order) on a running choice (prefix, mask, keys still to take); returns whether the chosen
 // bucket is needed whole (its count = the keys still to take: exactly `threshold` keys are then >= the
@@ -1360,8 +1371,11 @@ __device__ __forceinline__ uint64_t dim_key(const TopnSelJob& jb, int64_t id) {
 }
 
 // pass 0: metric keys, touched / row counts, histogram of the top byte
+// (PROG: the keys of a post-aggregator program; the plain instantiation carries none of its code or scratch)
+template <bool PROG>
 __global__ __launch_bounds__(kSelBlock) void k_topn_keys(const TopnSelJob* __restrict__ jobs, int naggs, int metric,
-                                                         int op, int kind, int inverted) {
+                                                         int op, int kind, int inverted,
+                                                         const TopnMetricProg* __restrict__ prog) {
   __shared__ unsigned int s_hist[256];
   __shared__ unsigned long long s_c, s_rows;
   const TopnSelJob& jb = jobs[blockIdx.y];
@@ -1382,7 +1396,8 @@ __global__ __launch_bounds__(kSelBlock) void k_topn_keys(const TopnSelJob* __res
       if (jb.dim_mode) {
         k = dim_key(jb, i);
       } else {
-        k = metric_key(jb.table[i * rec + 1 + metric], op, kind, inverted);
+        if constexpr (PROG) k = metric_prog_key(*prog, jb.table + i * rec + 1, inverted);
+        else k = metric_key(jb.table[i * rec + 1 + metric], op, kind, inverted);
         k = k ? k : 1;  // 0 marks untouched ids; a touched key of 0 becomes 1 (only widens the candidates)
       }
       if (k) atomicAdd(&s_hist[k >> 56], 1u);
@@ -1524,8 +1539,9 @@ __global__ __launch_bounds__(kSelBlock) void k_topn_compact(const TopnSelJob* __
 // order[k] = gather position of the k-th entry. Bitonic sort in LDS; skipped (order untouched)
 // when the candidates exceed kOrderCap (the host sorts then).
 constexpr int kOrderCap = 4096;
+template <bool PROG>
 __global__ __launch_bounds__(1024) void k_topn_order(const TopnSelJob* __restrict__ jobs, int naggs, int metric, int op,
-                                                     int kind, int inverted) {
+                                                     int kind, int inverted, const TopnMetricProg* __restrict__ prog) {
   __shared__ uint64_t s_key[kOrderCap];
   __shared__ uint16_t s_pos[kOrderCap];
   const TopnSelJob& jb = jobs[blockIdx.x];
@@ -1534,9 +1550,12 @@ __global__ __launch_bounds__(1024) void k_topn_order(const TopnSelJob* __restric
   int P = 1;
   while (P < n) P <<= 1;
   const int rec = naggs + 1;
-  auto key_of = [&](int c) {
+  auto key_of = [&](int c) -> uint64_t {
     const uint64_t* g = jb.gathered + (size_t)c * (rec + 1);
-    return c >= n ? 0ull : jb.dim_mode ? dim_key(jb, (int64_t)g[0]) : metric_key(g[1 + 1 + metric], op, kind, inverted);
+    if (c >= n) return 0ull;
+    if (jb.dim_mode) return dim_key(jb, (int64_t)g[0]);
+    if constexpr (PROG) return metric_prog_key(*prog, g + 2, inverted);
+    else return metric_key(g[1 + 1 + metric], op, kind, inverted);
   };
   if (P <= 1024) {
     // one element per thread: the compare-exchange stages of stride < 64 between the lanes of a
@@ -1623,18 +1642,26 @@ __global__ __launch_bounds__(1024) void k_topn_order(const TopnSelJob* __restric
 }
 
 void launch_topn_select(const TopnSelJob* d_jobs, int njobs, int64_t max_card, int naggs, int metric, int metric_op,
-                        int inverted, int threshold, hipStream_t s) {
+                        int inverted, int threshold, const TopnMetricProg* d_prog, hipStream_t s) {
   if (njobs <= 0 || max_card <= 0) return;
   const dim3 grid((unsigned)((max_card + kSelBlock - 1) / kSelBlock), (unsigned)njobs);
   // metric_op encodes (op << 8) | kind
-  hipLaunchKernelGGL(k_topn_keys, grid, dim3(kSelBlock), 0, s, d_jobs, naggs, metric, metric_op >> 8, metric_op & 255,
-                     inverted);
+  if (d_prog)
+    hipLaunchKernelGGL(k_topn_keys<true>, grid, dim3(kSelBlock), 0, s, d_jobs, naggs, metric, metric_op >> 8,
+                       metric_op & 255, inverted, d_prog);
+  else
+    hipLaunchKernelGGL(k_topn_keys<false>, grid, dim3(kSelBlock), 0, s, d_jobs, naggs, metric, metric_op >> 8,
+                       metric_op & 255, inverted, d_prog);
   for (int level = 1; level < 8; ++level)
     hipLaunchKernelGGL(k_topn_radix, grid, dim3(kSelBlock), 0, s, d_jobs, level, threshold);
   hipLaunchKernelGGL(k_topn_count, grid, dim3(kSelBlock), 0, s, d_jobs, threshold);
   hipLaunchKernelGGL(k_topn_compact, grid, dim3(kSelBlock), 0, s, d_jobs, naggs, threshold);
-  hipLaunchKernelGGL(k_topn_order, dim3((unsigned)njobs), dim3(1024), 0, s, d_jobs, naggs, metric, metric_op >> 8,
-                     metric_op & 255, inverted);
+  if (d_prog)
+    hipLaunchKernelGGL(k_topn_order<true>, dim3((unsigned)njobs), dim3(1024), 0, s, d_jobs, naggs, metric, metric_op >> 8,
+                       metric_op & 255, inverted, d_prog);
+  else
+    hipLaunchKernelGGL(k_topn_order<false>, dim3((unsigned)njobs), dim3(1024), 0, s, d_jobs, naggs, metric, metric_op >> 8,
+                       metric_op & 255, inverted, d_prog);
 }
 
 // ------------------------------------------------------------------------------------------------

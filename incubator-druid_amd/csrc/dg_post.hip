@@ -4,6 +4,7 @@
 //
 //   k_post_having     having tree (the HavingSpec classes of query/groupby/having) as a postfix program over each
 //                     group's slots -> selection bitset, one ballot per 64 groups (as k_num_pred)
+//   k_post_eval       post-aggregator programs (dg_postagg.h) over each group's slots -> value columns
 //   k_post_sort_word  one 64-bit word of the comparator chain (makeComparator :190-260) per element,
 //                     read through the element's group reference
 //
@@ -24,7 +25,9 @@ namespace dg {
 // outputs, Doubles.compare (every NaN equal and greatest, -0.0 < 0.0) for double outputs, the same over
 // the exactly widened float32 of float outputs (HavingSpecMetricComparator.java:36-80 compares doubles
 // the same way; DefaultLimitSpec.metricOrdering uses AggregatorFactory.getComparator).
+// A post column (kind = kPostColKind + its order kind) compares under the program's order kind.
 __device__ __forceinline__ uint64_t post_order_key(int kind, uint64_t v) {
+  if (kind >= kPostColKind) return pa_order_key(kind - kPostColKind, v);
   switch (kind) {
     case DG_AGG_COUNT:
     case DG_AGG_LONG_SUM:
@@ -52,7 +55,8 @@ __device__ __forceinline__ uint32_t post_order_key32(uint64_t v) {
 }
 
 __global__ __launch_bounds__(256) void k_post_having(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ slots,
-                                                     int64_t cap, int64_t n, PostHaving p, uint32_t* __restrict__ sel) {
+                                                     int64_t cap, int64_t n, PostHaving p, const uint64_t* __restrict__ post,
+                                                     uint32_t* __restrict__ sel) {
   const int lane = threadIdx.x & 63;
   for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
     const int64_t g = base + threadIdx.x;
@@ -72,7 +76,8 @@ __global__ __launch_bounds__(256) void k_post_having(const uint64_t* __restrict_
       } else if (op == DG_HAVING_AGG_RANGE) {
         uint64_t v = 0;
         if (live) {
-          const uint64_t k = post_order_key(p.kind[i], slots[(size_t)p.arg[i] * cap + g]);
+          const uint64_t* col = p.kind[i] >= kPostColKind ? post : slots;  // (arg: the column / the slot row)
+          const uint64_t k = post_order_key(p.kind[i], col[(size_t)p.arg[i] * cap + g]);
           v = k >= p.lo[i] && k <= p.hi[i];
         }
         st = (st << 1) | v;
@@ -92,15 +97,16 @@ __global__ __launch_bounds__(256) void k_post_having(const uint64_t* __restrict_
 }
 
 void launch_post_having(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n, const PostHaving& p,
-                        uint32_t* sel, hipStream_t s) {
+                        const uint64_t* post, uint32_t* sel, hipStream_t s) {
   if (n <= 0) return;
   const int64_t blocks = std::min<int64_t>(16384, (n + 255) / 256);
-  hipLaunchKernelGGL(k_post_having, dim3((unsigned)blocks), dim3(256), 0, s, keys, slots, cap, n, p, sel);
+  hipLaunchKernelGGL(k_post_having, dim3((unsigned)blocks), dim3(256), 0, s, keys, slots, cap, n, p, post, sel);
 }
 
 __global__ __launch_bounds__(256) void k_post_sort_word(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ slots,
                                                         int64_t cap, int64_t n, const unsigned long long* __restrict__ info,
                                                         const uint32_t* __restrict__ refs_in, PostWord w,
+                                                        const uint64_t* __restrict__ post,
                                                         uint64_t* __restrict__ kout, uint32_t* __restrict__ refs_out,
                                                         uint32_t* __restrict__ n_out) {
   int64_t count = n;
@@ -124,7 +130,8 @@ __global__ __launch_bounds__(256) void k_post_sort_word(const uint64_t* __restri
         v = (key >> pf.in_shift) & m;
         if (pf.rank) v = (uint64_t)(uint32_t)pf.rank[v];
       } else if (pf.type == POST_F_AGG64) {
-        v = post_order_key(pf.kind, slots[(size_t)pf.slot * cap + g]);
+        const uint64_t* col = pf.kind >= kPostColKind ? post : slots;  // (slot: the column / the slot row)
+        v = post_order_key(pf.kind, col[(size_t)pf.slot * cap + g]);
       } else {
         v = (uint64_t)post_order_key32(slots[(size_t)pf.slot * cap + g]);
       }
@@ -137,11 +144,33 @@ __global__ __launch_bounds__(256) void k_post_sort_word(const uint64_t* __restri
 }
 
 void launch_post_sort_word(const uint64_t* keys, const uint64_t* slots, int64_t cap, int64_t n,
-                           const unsigned long long* info, const uint32_t* refs_in, const PostWord& w, uint64_t* kout,
-                           uint32_t* refs_out, uint32_t* n_out, hipStream_t s) {
+                           const unsigned long long* info, const uint32_t* refs_in, const PostWord& w,
+                           const uint64_t* post, uint64_t* kout, uint32_t* refs_out, uint32_t* n_out, hipStream_t s) {
   const int64_t blocks = std::min<int64_t>(16384, std::max<int64_t>(1, (n + 255) / 256));
-  hipLaunchKernelGGL(k_post_sort_word, dim3((unsigned)blocks), dim3(256), 0, s, keys, slots, cap, n, info, refs_in, w, kout,
-                     refs_out, n_out);
+  hipLaunchKernelGGL(k_post_sort_word, dim3((unsigned)blocks), dim3(256), 0, s, keys, slots, cap, n, info, refs_in, w, post,
+                     kout, refs_out, n_out);
+}
+
+// Post-aggregator columns of a resident result (dg_result_post_aggregate): one group per lane, neighbouring
+// lanes hold neighbouring groups, so every slot read and the column store are contiguous per wave. The
+// programs are uniform across lanes (no divergence); the operand stack is per lane. The grid-stride loop is
+// bounded by n, and only groups below n are read or written (cap >= n).
+__global__ __launch_bounds__(256) void k_post_eval(const uint64_t* __restrict__ slots, int64_t cap, int64_t n,
+                                                   const PostAggProg* __restrict__ progs, int ncols,
+                                                   uint64_t* __restrict__ out) {
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+    for (int c = 0; c < ncols; ++c) {
+      const uint64_t v = pa_eval(progs[c], [&](int slot) { return slots[(size_t)(1 + slot) * cap + g]; });
+      out[(size_t)c * cap + g] = v;
+    }
+  }
+}
+
+void launch_post_eval(const uint64_t* slots, int64_t cap, int64_t n, const PostAggProg* d_progs, int ncols, uint64_t* out,
+                      hipStream_t s) {
+  if (n <= 0 || ncols <= 0) return;
+  const int64_t blocks = std::min<int64_t>(16384, (n + 255) / 256);
+  hipLaunchKernelGGL(k_post_eval, dim3((unsigned)blocks), dim3(256), 0, s, slots, cap, n, d_progs, ncols, out);
 }
 
 }  // namespace dg

@@ -102,6 +102,13 @@ def _refuse_pairs(query, what: str):
             raise R.N.UnsupportedQuery(2, f"{a.type}({a.name}): {what} does not combine first/last pairs")
 
 
+def _refuse_post_aggregations(query, what: str):
+    """The cross-process merges exchange aggregator slots only: a query with post-aggregators (whose topN
+    ranking and groupBy having / ORDER BY may depend on them) is refused before any collective."""
+    if getattr(query, "postAggregations", None):
+        raise R.N.UnsupportedQuery(2, f"{what} does not take post-aggregators")
+
+
 # ----------------------------------------------------------------------------------------------
 # timeseries
 # ----------------------------------------------------------------------------------------------
@@ -113,6 +120,7 @@ def allreduce_timeseries(dist, query: Q.TimeseriesQuery, local: List[Q.Result],
     ALL granularity); None derives it with one all_gather_object of the local keys. Ranks without
     data for a bucket contribute identities."""
     _refuse_pairs(query, "the cross-process timeseries reduce")
+    _refuse_post_aggregations(query, "the cross-process timeseries reduce")
     torch, _ = _torch()
     dev = _device(dist)
     gran = query.granularity
@@ -205,6 +213,7 @@ def gather_topn(dist, query: Q.TopNQuery, raw: "R.TopNRaw", gdict: GlobalDiction
     column) is refused: its result ids index per-segment value lists, which have no cluster-wide
     dictionary here."""
     _refuse_pairs(query, "the cross-process topN gather")
+    _refuse_post_aggregations(query, "the cross-process topN gather")
     if query.dimension_type != "STRING" or any(s.column_type(query.dimension) in R._NUMERIC_COLS
                                                for s in (segments or getattr(raw, "segments", None) or [])):
         raise R.N.UnsupportedQuery(2, f"topN on numeric dimension {query.dimension} across processes")
@@ -362,6 +371,7 @@ class GroupByExchange:
 
     def __init__(self, dist, query: Q.GroupByQuery, segments, engine=None):
         _refuse_pairs(query, "the cross-process groupBy merge")
+        _refuse_post_aggregations(query, "the cross-process groupBy merge")
         self.dist, self.query = dist, query
         self.world, self.rank = dist.get_world_size(), dist.get_rank()
         self.engine = engine if engine is not None else NativeMerge(segments[0].context)

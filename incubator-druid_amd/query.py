@@ -775,6 +775,456 @@ def float_last(name, field_name=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# post-aggregators (query/aggregation/post/*.java)
+# ----------------------------------------------------------------------------------------------
+def UnsupportedPostAggregator(msg: str):
+    """UnsupportedQuery for a post-aggregator the engine has no program for (javascript, expression,
+    hyperUniqueCardinality, a finalizingFieldAccess of anything but an aggregator): the caller keeps its CPU
+    engine."""
+    from ._native import UnsupportedQuery
+    return UnsupportedQuery(2, msg)
+
+
+# ops of a compiled post-aggregator program (DG_POST_* of include/druidgpu.h)
+POST_AGG, POST_CONST_D, POST_CONST_L, POST_L2D, POST_D2L = 0, 1, 2, 3, 4
+POST_ADD, POST_SUB, POST_MUL, POST_DIV, POST_QUOT = 5, 6, 7, 8, 9
+POST_DMAX, POST_DMIN, POST_LMAX, POST_LMIN = 10, 11, 12, 13
+POST_ORDER_NONE, POST_ORDER_DOUBLE, POST_ORDER_LONG, POST_ORDER_NUMERIC_FIRST = 0, 1, 2, 3
+POST_MAX_OPS, POST_MAX_STACK = 64, 16
+_ARITH_OPS = {"+": POST_ADD, "-": POST_SUB, "*": POST_MUL, "/": POST_DIV, "quotient": POST_QUOT}
+
+
+def double_bits(d: float) -> int:
+    """Double.doubleToLongBits as an unsigned number (every NaN is the canonical one)."""
+    if d != d:
+        return 0x7FF8000000000000
+    return struct.unpack("<Q", struct.pack("<d", d))[0]
+
+
+def java_d2l(d: float) -> int:
+    """Java's (long) double (JLS 5.1.3): NaN -> 0, saturating at Long.MIN_VALUE / MAX_VALUE, else truncation."""
+    if d != d:
+        return 0
+    if d >= 9223372036854775808.0:
+        return LONG_MAX
+    if d <= -9223372036854775808.0:
+        return LONG_MIN
+    return int(d)
+
+
+def java_double_compare(a: float, b: float) -> int:
+    """Double.compare: numeric order, -0.0 < 0.0, NaN equal to NaN and greater than everything else."""
+    if a < b:
+        return -1
+    if a > b:
+        return 1
+    x, y = double_bits(a), double_bits(b)
+    x = x - (1 << 64) if x >> 63 else x
+    y = y - (1 << 64) if y >> 63 else y
+    return (x > y) - (x < y)
+
+
+def java_double_div(lhs: float, rhs: float) -> float:
+    """IEEE lhs / rhs (Python raises on a zero divisor)."""
+    if rhs != 0.0 or rhs != rhs:
+        return lhs / rhs
+    if lhs != lhs or lhs == 0.0:
+        return math.nan
+    return math.copysign(math.inf, lhs) * math.copysign(1.0, rhs)
+
+
+def _number_to_double(v) -> float:
+    return float(v)  # Number.doubleValue: a long rounds to nearest even, a float widens exactly
+
+
+def _number_to_long(v) -> int:
+    return int(v) if isinstance(v, int) else java_d2l(float(v))  # Number.longValue
+
+
+class PostAggregator:
+    """One post-aggregator: `name`, to_json, compute(event) — the host restatement over a row's values, Python
+    floats being IEEE doubles — and emit(ctx), which appends the postfix program of include/druidgpu.h to ctx.ops
+    and returns the value's type ("long" / "double")."""
+    order = POST_ORDER_DOUBLE
+
+    def compute(self, event: Dict[str, Any]):
+        raise NotImplementedError
+
+    def emit(self, ctx: "_PostCompile") -> str:
+        raise NotImplementedError
+
+    def dependent_fields(self) -> List[str]:
+        return []
+
+    def order_kind(self, ctx: "_PostCompile") -> int:
+        """The comparator (getComparator) as a POST_ORDER_* kind."""
+        return self.order
+
+    @staticmethod
+    def from_json(js) -> "PostAggregator":
+        if isinstance(js, PostAggregator):
+            return js
+        t = js.get("type")
+        if t == "arithmetic":
+            return ArithmeticPostAggregator(js.get("name"), js["fn"], [PostAggregator.from_json(f) for f in js["fields"]],
+                                            js.get("ordering"))
+        if t == "fieldAccess":
+            return FieldAccessPostAggregator(js.get("name"), js["fieldName"])
+        if t == "finalizingFieldAccess":
+            return FinalizingFieldAccessPostAggregator(js.get("name"), js["fieldName"])
+        if t == "constant":
+            return ConstantPostAggregator(js.get("name"), js["value"])
+        if t in _GREATEST_LEAST:
+            return _GREATEST_LEAST[t](js.get("name"), [PostAggregator.from_json(f) for f in js["fields"]])
+        if t in ("javascript", "expression", "hyperUniqueCardinality"):
+            raise UnsupportedPostAggregator(f"post-aggregator type {t!r} stays on the CPU engine")
+        raise ValueError(f"unknown post-aggregator type {t!r}")
+
+
+class _PostCompile:
+    """State of one compilation: the aggregators' native slots and the earlier post-aggregators a field may
+    name (Queries.prepareAggregations: an earlier one is inlined)."""
+
+    def __init__(self, aggregations: Sequence[AggregatorFactory], earlier: Dict[str, PostAggregator]):
+        self.aggs = {a.name: (i, a) for a, i in zip(aggregations, native_index(aggregations))}
+        self.earlier = earlier
+        self.ops: List[Tuple[int, int, int]] = []  # (op, arg, imm)
+
+    def push(self, op: int, arg: int = 0, imm: int = 0):
+        self.ops.append((op, arg, imm & ((1 << 64) - 1)))
+
+    def to_double(self, t: str):
+        if t == "long":
+            self.push(POST_L2D)
+
+    def to_long(self, t: str):
+        if t == "double":
+            self.push(POST_D2L)
+
+
+@dataclass
+class FieldAccessPostAggregator(PostAggregator):
+    """FieldAccessPostAggregator.java: the row's value of `fieldName` as it is."""
+    name: Optional[str]
+    fieldName: str
+
+    def dependent_fields(self):
+        return [self.fieldName]
+
+    def compute(self, event):
+        return event[self.fieldName]
+
+    def emit(self, ctx):
+        if self.fieldName in ctx.aggs:
+            i, a = ctx.aggs[self.fieldName]
+            if a.is_pair:  # a SerializablePair is not a Number: the reference's cast fails
+                raise ValueError(f"fieldAccess of the first/last aggregator {self.fieldName!r} is a pair, not a number "
+                                 "(use finalizingFieldAccess)")
+            ctx.push(POST_AGG, i)
+            return "long" if a.output_type == "long" else "double"
+        if self.fieldName in ctx.earlier:
+            return ctx.earlier[self.fieldName].emit(ctx)
+        raise ValueError(f"post-aggregator field {self.fieldName!r} names no aggregator and no earlier post-aggregator")
+
+    def order_kind(self, ctx):
+        raise ValueError("a fieldAccess post-aggregator has no comparator (FieldAccessPostAggregator.getComparator)")
+
+    def to_json(self):
+        return {"type": "fieldAccess", "name": self.name, "fieldName": self.fieldName}
+
+
+@dataclass
+class FinalizingFieldAccessPostAggregator(PostAggregator):
+    """FinalizingFieldAccessPostAggregator.java: AggregatorFactory.finalizeComputation of the row's value; its
+    comparator is the aggregator's."""
+    name: Optional[str]
+    fieldName: str
+
+    def dependent_fields(self):
+        return [self.fieldName]
+
+    def compute(self, event):
+        v = event[self.fieldName]
+        return v.rhs if isinstance(v, SerializablePair) else v
+
+    def emit(self, ctx):
+        if self.fieldName not in ctx.aggs:
+            raise UnsupportedPostAggregator(f"finalizingFieldAccess of {self.fieldName!r}, which is no aggregator")
+        i, a = ctx.aggs[self.fieldName]
+        ctx.push(POST_AGG, i)  # (a first/last pair's value slot; its time is the slot after it)
+        return "long" if a.output_type == "long" else "double"
+
+    def order_kind(self, ctx):
+        if self.fieldName not in ctx.aggs:
+            raise UnsupportedPostAggregator(f"finalizingFieldAccess of {self.fieldName!r}, which is no aggregator")
+        return POST_ORDER_LONG if ctx.aggs[self.fieldName][1].output_type == "long" else POST_ORDER_DOUBLE
+
+    def to_json(self):
+        return {"type": "finalizingFieldAccess", "name": self.name, "fieldName": self.fieldName}
+
+
+@dataclass
+class ConstantPostAggregator(PostAggregator):
+    """ConstantPostAggregator.java: a number; its comparator calls every two values equal."""
+    name: Optional[str]
+    value: Any
+    order = POST_ORDER_NONE
+
+    def __post_init__(self):
+        if isinstance(self.value, bool) or not isinstance(self.value, (int, float)):
+            raise ValueError("Constant value must be a number")
+        if isinstance(self.value, int) and not LONG_MIN <= self.value <= LONG_MAX:
+            raise ValueError("Constant value out of the long range")
+
+    def compute(self, event):
+        return self.value
+
+    def emit(self, ctx):
+        if isinstance(self.value, int):
+            ctx.push(POST_CONST_L, 0, self.value)
+            return "long"
+        ctx.push(POST_CONST_D, 0, double_bits(self.value))
+        return "double"
+
+    def to_json(self):
+        return {"type": "constant", "name": self.name, "value": self.value}
+
+
+@dataclass
+class ArithmeticPostAggregator(PostAggregator):
+    """ArithmeticPostAggregator.java: a left fold of `fn` over the fields' doubleValue() (:107-124); "/" gives 0
+    for a zero divisor (:229-235), "quotient" is IEEE division; ordering None = Double.compare, "numericFirst" =
+    Ordering.numericFirst (:277-299)."""
+    name: Optional[str]
+    fn: str
+    fields: List[PostAggregator]
+    ordering: Optional[str] = None
+
+    def __post_init__(self):
+        self.fields = [PostAggregator.from_json(f) for f in self.fields]
+        if self.fn not in _ARITH_OPS:
+            raise ValueError(f"Unknown operation[{self.fn}], known operations[{sorted(_ARITH_OPS)}]")
+        if len(self.fields) < 2:
+            raise ValueError(f"Illegal number of fields[{len(self.fields)}], must be > 1")
+        if self.ordering not in (None, "numericFirst"):
+            raise ValueError(f"unknown ordering {self.ordering!r}")
+
+    @property
+    def order(self):
+        return POST_ORDER_NUMERIC_FIRST if self.ordering == "numericFirst" else POST_ORDER_DOUBLE
+
+    def dependent_fields(self):
+        return [d for f in self.fields for d in f.dependent_fields()]
+
+    def _apply(self, lhs: float, rhs: float) -> float:
+        if self.fn == "+":
+            return lhs + rhs
+        if self.fn == "-":
+            return lhs - rhs
+        if self.fn == "*":
+            return lhs * rhs
+        if self.fn == "/":
+            return 0.0 if rhs == 0.0 else lhs / rhs  # (-0.0 == 0.0; a NaN divisor is not zero)
+        return java_double_div(lhs, rhs)
+
+    def compute(self, event):
+        vals = []
+        for f in self.fields:
+            v = f.compute(event)
+            if isinstance(v, SerializablePair):
+                raise ValueError("a first/last pair is not a number (use finalizingFieldAccess)")
+            vals.append(_number_to_double(v))
+        acc = vals[0]
+        for v in vals[1:]:
+            acc = self._apply(acc, v)
+        return acc
+
+    def emit(self, ctx):
+        ctx.to_double(self.fields[0].emit(ctx))
+        for f in self.fields[1:]:
+            ctx.to_double(f.emit(ctx))
+            ctx.push(_ARITH_OPS[self.fn])
+        return "double"
+
+    def to_json(self):
+        js = {"type": "arithmetic", "name": self.name, "fn": self.fn, "fields": [f.to_json() for f in self.fields]}
+        if self.ordering is not None:
+            js["ordering"] = self.ordering
+        return js
+
+
+@dataclass
+class _GreatestLeast(PostAggregator):
+    name: Optional[str]
+    fields: List[PostAggregator]
+    type_name = ""
+    is_long = False
+    greatest = True
+
+    def __post_init__(self):
+        self.fields = [PostAggregator.from_json(f) for f in self.fields]
+        if not self.fields:
+            raise ValueError("Illegal number of fields[0], must be > 0")
+
+    @property
+    def order(self):
+        return POST_ORDER_LONG if self.is_long else POST_ORDER_DOUBLE
+
+    def dependent_fields(self):
+        return [d for f in self.fields for d in f.dependent_fields()]
+
+    def compute(self, event):
+        # DoubleGreatestPostAggregator.java:77-92 (and its three siblings): folded from the type's least /
+        # greatest value, a field replaces the running value when the comparator says strictly greater / less
+        if self.is_long:
+            acc = LONG_MIN if self.greatest else LONG_MAX
+        else:
+            acc = -math.inf if self.greatest else math.inf
+        for f in self.fields:
+            v = f.compute(event)
+            if isinstance(v, SerializablePair):
+                raise ValueError("a first/last pair is not a number (use finalizingFieldAccess)")
+            if self.is_long:
+                v = _number_to_long(v)
+                c = (v > acc) - (v < acc)
+            else:
+                v = _number_to_double(v)
+                c = java_double_compare(v, acc)
+            if (c > 0) if self.greatest else (c < 0):
+                acc = v
+        return acc
+
+    def emit(self, ctx):
+        if self.is_long:
+            ctx.push(POST_CONST_L, 0, LONG_MIN if self.greatest else LONG_MAX)
+        else:
+            ctx.push(POST_CONST_D, 0, double_bits(-math.inf if self.greatest else math.inf))
+        for f in self.fields:
+            t = f.emit(ctx)
+            if self.is_long:
+                ctx.to_long(t)
+                ctx.push(POST_LMAX if self.greatest else POST_LMIN)
+            else:
+                ctx.to_double(t)
+                ctx.push(POST_DMAX if self.greatest else POST_DMIN)
+        return "long" if self.is_long else "double"
+
+    def to_json(self):
+        return {"type": self.type_name, "name": self.name, "fields": [f.to_json() for f in self.fields]}
+
+
+class DoubleGreatestPostAggregator(_GreatestLeast):
+    type_name, is_long, greatest = "doubleGreatest", False, True
+
+
+class DoubleLeastPostAggregator(_GreatestLeast):
+    type_name, is_long, greatest = "doubleLeast", False, False
+
+
+class LongGreatestPostAggregator(_GreatestLeast):
+    type_name, is_long, greatest = "longGreatest", True, True
+
+
+class LongLeastPostAggregator(_GreatestLeast):
+    type_name, is_long, greatest = "longLeast", True, False
+
+
+_GREATEST_LEAST = {c.type_name: c for c in (DoubleGreatestPostAggregator, DoubleLeastPostAggregator,
+                                            LongGreatestPostAggregator, LongLeastPostAggregator)}
+
+
+@dataclass
+class PostProgram:
+    """A compiled post-aggregator: ops = [(op, arg, imm)] in postfix order, the value's type and the
+    comparator's order kind."""
+    ops: List[Tuple[int, int, int]]
+    out_type: str
+    order: int
+
+
+def compile_post_aggregator(aggregations: Sequence[AggregatorFactory], post_aggregations: Sequence[PostAggregator],
+                            name: str, for_order: bool = True) -> PostProgram:
+    """The program of the query's post-aggregator `name` over the native slots of `aggregations`. for_order: the
+    order kind is the post-aggregator's comparator (ValueError when it has none); otherwise (a having leaf, which
+    compares numbers with HavingSpecMetricComparator) the value type's natural order. Programs beyond the ABI's
+    length or stack are UnsupportedPostAggregator."""
+    earlier: Dict[str, PostAggregator] = {}
+    target = None
+    for p in post_aggregations:
+        if p.name == name:
+            target = p
+            break
+        earlier[p.name] = p
+    if target is None:
+        raise ValueError(f"no post-aggregator named {name!r}")
+    ctx = _PostCompile(aggregations, earlier)
+    out_type = target.emit(ctx)
+    if for_order:
+        order = target.order_kind(ctx)
+    else:
+        order = POST_ORDER_LONG if out_type == "long" else POST_ORDER_DOUBLE
+    if len(ctx.ops) > POST_MAX_OPS:
+        raise UnsupportedPostAggregator(f"post-aggregator {name!r} compiles to {len(ctx.ops)} ops (max {POST_MAX_OPS})")
+    depth = 0
+    for op, _, _ in ctx.ops:
+        depth += 1 if op <= POST_CONST_L else (0 if op <= POST_D2L else -1)
+        if depth > POST_MAX_STACK:
+            raise UnsupportedPostAggregator(f"post-aggregator {name!r} needs more than {POST_MAX_STACK} stack entries")
+    return PostProgram(ctx.ops, out_type, order)
+
+
+def post_program_order_key(order: int, word: int) -> int:
+    """The unsigned order key of a program's raw 64-bit value under its order kind (pa_order_key of the engine):
+    comparator order = key order."""
+    sign = 1 << 63
+    if order == POST_ORDER_NONE:
+        return 0
+    if order == POST_ORDER_LONG:
+        return word ^ sign
+    d = struct.unpack("<d", struct.pack("<Q", word))[0]
+    if d != d:
+        return 2 if order == POST_ORDER_NUMERIC_FIRST else (1 << 64) - 1
+    if order == POST_ORDER_NUMERIC_FIRST and math.isinf(d):
+        return 0 if d < 0 else 1
+    return (~word & ((1 << 64) - 1)) if word & sign else (word | sign)
+
+
+def post_value_word(v, out_type: str) -> int:
+    """A post-aggregator value as the raw word a program leaves."""
+    return (int(v) & ((1 << 64) - 1)) if out_type == "long" else double_bits(float(v))
+
+
+def parse_post_aggregations(aggregations: Sequence[AggregatorFactory], post_aggregations) -> List[PostAggregator]:
+    """Queries.prepareAggregations: names unique among aggregators and post-aggregators; every field names an
+    aggregator or an EARLIER post-aggregator."""
+    out = [PostAggregator.from_json(p) for p in (post_aggregations or [])]
+    names = {a.name for a in aggregations}
+    for p in out:
+        if p.name is None:
+            raise ValueError("a top-level post-aggregator needs a name")
+        for f in p.dependent_fields():
+            if f not in names:
+                raise ValueError(f"Missing fields [{f}] for postAggregator [{p.name}]")
+        if p.name in names:
+            raise ValueError(f"[{p.name}] already defined")
+        names.add(p.name)
+    return out
+
+
+def compute_post_aggregations(query, event: Dict[str, Any]) -> Dict[str, Any]:
+    """The row with every post-aggregator's value added, in order (a later one may read an earlier one)."""
+    for p in getattr(query, "postAggregations", None) or []:
+        event[p.name] = p.compute(event)
+    return event
+
+
+def post_compare_key(p: PostAggregator, query, v):
+    """Sort key realising the post-aggregator's comparator over its computed values."""
+    prog = compile_post_aggregator(query.aggregations, query.postAggregations, p.name, True)
+    return post_program_order_key(prog.order, post_value_word(v, prog.out_type))
+
+
+# ----------------------------------------------------------------------------------------------
 # topN metric specs
 # ----------------------------------------------------------------------------------------------
 @dataclass
@@ -860,9 +1310,21 @@ class BaseQuery:
         return js
 
 
+def _with_post_aggregations(js, query):
+    """postAggregations only when there are some: a query without them serializes as it always did."""
+    if query.postAggregations:
+        js["postAggregations"] = [p.to_json() for p in query.postAggregations]
+    return js
+
+
 @dataclass
 class TimeseriesQuery(BaseQuery):
     descending: bool = False
+    postAggregations: List = field(default_factory=list)
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.postAggregations = parse_post_aggregations(self.aggregations, self.postAggregations)
 
     @property
     def skip_empty_buckets(self) -> bool:
@@ -871,7 +1333,7 @@ class TimeseriesQuery(BaseQuery):
     def to_json(self):
         js = self._base_json("timeseries")
         js["descending"] = self.descending
-        return js
+        return _with_post_aggregations(js, self)
 
 
 @dataclass
@@ -882,6 +1344,7 @@ class TopNQuery(BaseQuery):
     metric: Any = None
     threshold: int = 10
     dimension_type: str = "STRING"
+    postAggregations: List = field(default_factory=list)
 
     def __post_init__(self):
         super().__post_init__()
@@ -894,9 +1357,23 @@ class TopNQuery(BaseQuery):
         self.dimension_type = str(self.dimension_type).upper()
         if self.dimension_type not in DIMENSION_OUTPUT_TYPES:
             raise ValueError(f"unknown outputType {self.dimension_type!r}")
+        self.postAggregations = parse_post_aggregations(self.aggregations, self.postAggregations)
         self.metric = TopNMetricSpec.of(self.metric)
         if self.metric.type in ("numeric", "inverted") and self.metric.metric not in {a.name for a in self.aggregations}:
-            raise ValueError("topN metric must name an aggregator")
+            if self.metric.metric in {p.name for p in self.postAggregations}:
+                self.metric_program()  # (ValueError: no comparator; UnsupportedQuery: no program)
+            else:
+                raise ValueError("topN metric must name an aggregator")
+
+    def metric_program(self) -> Optional["PostProgram"]:
+        """The program of the post-aggregator a numeric / inverted metric spec names (NumericTopNMetricSpec.
+        getComparator takes the post-aggregator's comparator), or None when it names an aggregator."""
+        if self.metric.type not in ("numeric", "inverted") or self.metric.metric in {a.name for a in self.aggregations}:
+            return None
+        prog = compile_post_aggregator(self.aggregations, self.postAggregations, self.metric.metric, True)
+        if prog.order == POST_ORDER_NONE:
+            raise UnsupportedPostAggregator("topN ranked by a constant post-aggregator (every value ties)")
+        return prog
 
     @property
     def min_topn_threshold(self) -> int:
@@ -914,7 +1391,7 @@ class TopNQuery(BaseQuery):
         if self.dimension_type != "STRING":
             dim = {"type": "default", "dimension": dim, "outputName": dim, "outputType": self.dimension_type}
         js.update({"dimension": dim, "metric": self.metric.to_json(), "threshold": self.threshold})
-        return js
+        return _with_post_aggregations(js, self)
 
 
 @dataclass
@@ -1032,6 +1509,7 @@ class GroupByQuery(BaseQuery):
     limitSpec: Optional[DefaultLimitSpec] = None
     having: Optional[HavingSpec] = None
     dimensionTypes: Optional[List[str]] = None
+    postAggregations: List = field(default_factory=list)
 
     def __post_init__(self):
         super().__post_init__()
@@ -1063,6 +1541,15 @@ class GroupByQuery(BaseQuery):
             types.append(t)
         self.dimensions = dims
         self.dimensionTypes = types
+        self.postAggregations = parse_post_aggregations(self.aggregations, self.postAggregations)
+        if any(p.name in dims for p in self.postAggregations):
+            raise ValueError("a post-aggregator has the name of a dimension")
+
+    def post_aggregator(self, name: str) -> Optional["PostAggregator"]:
+        for p in self.postAggregations:
+            if p.name == name:
+                return p
+        return None
 
     def dimension_type(self, name: str) -> str:
         """The output type of the grouping dimension `name` (STRING for anything else)."""
@@ -1129,7 +1616,7 @@ class GroupByQuery(BaseQuery):
             js["limitSpec"] = self.limitSpec.to_json()
         if self.having is not None:
             js["having"] = self.having.to_json()
-        return js
+        return _with_post_aggregations(js, self)
 
 
 SEARCH_SPEC_TYPES = ("contains", "insensitive_contains", "fragment", "regex", "all")
@@ -1317,13 +1804,16 @@ def query_from_json(js: Dict[str, Any]):
     common = dict(dataSource=js.get("dataSource", "ds"), intervals=js["intervals"],
                   granularity=js.get("granularity", "all"), filter=js.get("filter"),
                   aggregations=js.get("aggregations", []), context=js.get("context", {}) or {})
+    post = js.get("postAggregations") or []
     if qt == "timeseries":
-        return TimeseriesQuery(descending=bool(js.get("descending", False)), **common)
+        return TimeseriesQuery(descending=bool(js.get("descending", False)), postAggregations=post, **common)
     if qt == "topN":
-        return TopNQuery(dimension=js["dimension"], metric=js["metric"], threshold=int(js["threshold"]), **common)
+        return TopNQuery(dimension=js["dimension"], metric=js["metric"], threshold=int(js["threshold"]),
+                         postAggregations=post, **common)
     if qt == "groupBy":
         return GroupByQuery(dimensions=js.get("dimensions", []), limitSpec=js.get("limitSpec"),
-                            having=js.get("having"), dimensionTypes=js.get("dimensionTypes"), **common)
+                            having=js.get("having"), dimensionTypes=js.get("dimensionTypes"), postAggregations=post,
+                            **common)
     if qt == "search":
         return SearchQuery(searchDimensions=js.get("searchDimensions") or [], query=js.get("query"),
                            sort=js.get("sort") or "lexicographic", limit=int(js.get("limit", 0) or 0), **common)

@@ -241,8 +241,9 @@ def run_timeseries(segments: Sequence[GpuSegment], query: Q.TimeseriesQuery,
                                         ctypes.byref(on), o_t.ctypes.data, None, o_v.ctypes.data))
     m = on.value
     cols = _decode_slots(query.aggregations, o_v.reshape(-1, max(na, 1))[:m, :na])
-    return [Q.Result(int(o_t[b]), {a.name: _py(c[b], a.output_type) for a, c in zip(query.aggregations, cols)})
-            for b in range(m)]
+    # post-aggregators after the merge, from the merged aggregators (TimeseriesQueryQueryToolChest.java:378-386)
+    return [Q.Result(int(o_t[b]), Q.compute_post_aggregations(
+        query, {a.name: _py(c[b], a.output_type) for a, c in zip(query.aggregations, cols)})) for b in range(m)]
 
 
 def _bucket_cap(segs, query) -> int:
@@ -277,6 +278,8 @@ def merge_timeseries(query: Q.TimeseriesQuery, per_segment: List[List[Q.Result]]
             for a in query.aggregations:
                 acc[a.name] = a.combine(acc[a.name], r.value[a.name])
     out = [merged[k] for k in sorted(merged)]
+    for r in out:  # (TimeseriesQueryQueryToolChest.java:378-386: from the merged aggregators)
+        Q.compute_post_aggregations(query, r.value)
     if query.descending:
         out.reverse()
     return out
@@ -352,7 +355,9 @@ class TopNResultBuilder:
 
     def __init__(self, query: Q.TopNQuery, threshold: int):
         spec = query.metric
-        agg = next(a for a in query.aggregations if a.name == spec.metric)
+        # a metric naming a post-aggregator ranks under its comparator (NumericTopNMetricSpec.getComparator)
+        self.prog = query.metric_program()
+        agg = None if self.prog is not None else next(a for a in query.aggregations if a.name == spec.metric)
         self.metric = spec.metric
         self.dim = query.dimension
         self.inverted = spec.type == "inverted"
@@ -363,7 +368,10 @@ class TopNResultBuilder:
         self.heap: List[_HeapItem] = []
 
     def _mk(self, v):
-        k = self.agg.compare_key(v)
+        if self.prog is not None:
+            k = Q.post_program_order_key(self.prog.order, Q.post_value_word(v, self.prog.out_type))
+        else:
+            k = self.agg.compare_key(v)
         return _Rev(k) if self.inverted else k
 
     def add(self, entry: Dict):
@@ -567,8 +575,10 @@ def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence
             t.min_rank = mins.ctypes.data
             keep.append(mins)
     else:
-        # (the native slot of the metric's value: a first/last aggregator orders by its pair's rhs)
-        t.metric_agg = Q.native_index(query.aggregations)[[a.name for a in query.aggregations].index(spec.metric)]
+        # (the native slot of the metric's value: a first/last aggregator orders by its pair's rhs; a metric
+        # naming a post-aggregator travels as a program, _topn_metric, and the slot is ignored)
+        names = [a.name for a in query.aggregations]
+        t.metric_agg = Q.native_index(query.aggregations)[names.index(spec.metric)] if spec.metric in names else 0
         t.inverted = int(spec.type == "inverted")
         t.dim_order = -1
     return t, keep
@@ -576,6 +586,15 @@ def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence
 
 def _check_topn(query: Q.TopNQuery):
     pass
+
+
+def _topn_metric(query: Q.TopNQuery):
+    """The trailing program of dg_topn_run_post / dg_topn_merge_post: (pointer or None, keep-alive)."""
+    prog = query.metric_program()
+    if prog is None:
+        return None, None
+    arr, keep = N.make_post_aggs([(prog.ops, prog.order)])
+    return arr, (arr, keep)
 
 
 def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional[RunStats] = None,
@@ -607,7 +626,8 @@ def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
         cut = np.zeros(n * bcap, dtype=np.int32)
         opts = ctypes.byref(_topn_opts(query, cut))
     m = N.dg_metrics()
-    N.check(N.lib().dg_topn_run_opts(_handles(segments), n, ctypes.byref(scan), ctypes.byref(t), opts,
+    metric, keep_m = _topn_metric(query)
+    N.check(N.lib().dg_topn_run_post(_handles(segments), n, ctypes.byref(scan), ctypes.byref(t), opts, metric,
                                      cnt.ctypes.data, ids.ctypes.data, vals.ctypes.data, ctypes.byref(m)))
     if stats is not None:
         stats.add(m)
@@ -656,7 +676,8 @@ def topn_merge_raw(query: Q.TopNQuery, cnt: np.ndarray, keys: np.ndarray, vals: 
     if handles is not None:
         hs = (ctypes.c_void_p * n)(*[handles[i] for i in order])
     opts = None if query.dimension_type == "STRING" else ctypes.byref(_topn_opts(query))  # (None: output STRING)
-    N.check(N.lib().dg_topn_merge_opts(hs, ctypes.byref(scan), ctypes.byref(t), ctypes.byref(lists), opts,
+    metric, keep_m = _topn_metric(query)
+    N.check(N.lib().dg_topn_merge_post(hs, ctypes.byref(scan), ctypes.byref(t), ctypes.byref(lists), opts, metric,
                                        ctypes.byref(out_n), out_list.ctypes.data, out_keys.ctypes.data,
                                        out_vals.ctypes.data))
     k = out_n.value
@@ -675,7 +696,8 @@ def _topn_entries(query: Q.TopNQuery, values: List[Optional[str]], slots) -> Lis
         e = {dim: v}
         for name, col in zip(names, cols):
             e[name] = col[j]
-        out.append(e)
+        # every post-aggregator's value, from the entry's aggregators (TopNQueryQueryToolChest.java:196-206)
+        out.append(Q.compute_post_aggregations(query, e))
     return out
 
 
@@ -806,7 +828,8 @@ def topn_binary_fn(query: Q.TopNQuery, r1: Optional[Q.Result], r2: Optional[Q.Re
             c = {dim: v[dim]}
             for agg in query.aggregations:
                 c[agg.name] = agg.combine(a[agg.name], v[agg.name])
-            ret[k] = c
+            # recomputed after the combine, before the builder ranks (TopNBinaryFn.java:97-110)
+            ret[k] = Q.compute_post_aggregations(query, c)
         else:
             ret[k] = v
     bob = _result_builder(query, query.threshold)
@@ -916,6 +939,8 @@ class GroupByResult:
         self._dicts = dictionaries
         self.time_map: Optional[np.ndarray] = None  # bucket index -> time (a dg_merge over a calendar grid)
         self.post_info: Optional[Dict] = None  # dg_post_info of apply_post_process, once it ran
+        self.post_programs: List = []          # post_process_spec: the programs of dg_result_post_aggregate
+        self.post_aggregate_ms = 0.0           # its device time
 
     def dim_types(self, d: int) -> Tuple[int, int]:
         """(column type, output type) of dimension d as N.COL_* (dg_result_dim_type); a dg_merge result has
@@ -1037,9 +1062,11 @@ class GroupByResult:
         if q.having is None and ls is None:
             return None
         ops: List = []
+        post = PostColumns(q)
+        self.post_programs = post.programs
         if q.having is not None:
             try:
-                ops = having_program(q, self.dictionary)
+                ops = having_program(q, self.dictionary, post)
             except (ValueError, ArithmeticError):  # (a value the comparator itself refuses: the host path raises it)
                 return None
             if ops is None:
@@ -1054,6 +1081,9 @@ class GroupByResult:
             for c in ls.columns if sort else []:
                 if c.dimension in aggs:
                     cols.append((N.ORDER_AGG, aggs[c.dimension], c.direction == "descending", None))
+                elif q.post_aggregator(c.dimension) is not None:
+                    # post column j is "aggregator" n_aggs + j, compared under the post-aggregator's comparator
+                    cols.append((N.ORDER_AGG, post.index(c.dimension, True), c.direction == "descending", None))
                 elif c.dimension in q.dimensions:
                     d = q.dimensions.index(c.dimension)
                     if q.dimensionTypes[d] != "STRING":
@@ -1067,6 +1097,8 @@ class GroupByResult:
                     return None
             if ls.limit is not None and ls.limit < (1 << 31):
                 limit = int(ls.limit)
+        if len(post.programs) > N.POST_MAX_COLS:
+            return None
         return ops, cols, sort, limit
 
     def apply_post_process(self) -> bool:
@@ -1082,6 +1114,12 @@ class GroupByResult:
         if spec is None:
             return False
         ops, cols, sort, limit = spec
+        if self.post_programs:  # the post-aggregators the having or the limit spec decides on, as columns
+            parr, keep = N.make_post_aggs(self.post_programs)
+            ms = ctypes.c_double()
+            N.check(N.lib().dg_result_post_aggregate(self.handle, parr, len(self.post_programs), ctypes.byref(ms)))
+            self.post_aggregate_ms = ms.value
+            del keep
         harr = (N.dg_having_op * max(len(ops), 1))(*[N.dg_having_op(*o) for o in ops])
         carr = (N.dg_post_column * max(len(cols), 1))(
             *[N.dg_post_column(k, i, int(desc), 0, rank.ctypes.data if rank is not None else None)
@@ -1490,7 +1528,7 @@ def _limit_needs_sort(query: Q.GroupByQuery) -> bool:
     ls = query.limitSpec
     if len(query.dimensions) < len(ls.columns):
         return True
-    aggs = {a.name for a in query.aggregations}
+    aggs = {a.name for a in query.aggregations} | {p.name for p in query.postAggregations}
     for i, c in enumerate(ls.columns):
         if c.dimension in aggs:
             return True
@@ -1570,7 +1608,34 @@ def having_interval(kind: str, out_type: str, value) -> Tuple[int, int]:
     return (lo, hi) if 0 <= lo <= hi <= _KEY_MAX else (1, 0)
 
 
-def having_program(query: Q.GroupByQuery, dictionary) -> Optional[List[Tuple[int, int, int, int]]]:
+class PostColumns:
+    """The post-aggregator columns one dg_result_post_aggregate call evaluates for a query's having and limit
+    specs: index(name, for_order) gives the "aggregator" index n_aggs + j of the column (dg_result_post_process),
+    one column per (post-aggregator, order kind). for_order: the post-aggregator's own comparator (an ORDER BY
+    column); otherwise the value type's natural order, which HavingSpecMetricComparator's intervals are cut in."""
+
+    def __init__(self, query: Q.GroupByQuery):
+        self.query = query
+        self.n_aggs = _native_width(query)
+        self.programs: List[Tuple[List[Tuple[int, int, int]], int]] = []
+        self.out_types: List[str] = []
+        self._at: Dict[Tuple[str, int], int] = {}
+
+    def index(self, name: str, for_order: bool) -> int:
+        prog = Q.compile_post_aggregator(self.query.aggregations, self.query.postAggregations, name, for_order)
+        k = (name, prog.order)
+        if k not in self._at:
+            self._at[k] = len(self.programs)
+            self.programs.append((prog.ops, prog.order))
+            self.out_types.append(prog.out_type)
+        return self.n_aggs + self._at[k]
+
+    def out_type(self, index: int) -> str:
+        return self.out_types[index - self.n_aggs]
+
+
+def having_program(query: Q.GroupByQuery, dictionary,
+                   post: Optional[PostColumns] = None) -> Optional[List[Tuple[int, int, int, int]]]:
     """query.having as dg_having_op tuples (op, arg, lo, hi) in postfix order, or None when it cannot be
     expressed (a leaf on a LONG-output dimension, a metric leaf naming a dimension, a value that is no
     number, a program beyond the ABI's length or stack). dictionary(d): the result's merged dictionary
@@ -1619,6 +1684,15 @@ def having_program(query: Q.GroupByQuery, dictionary) -> Optional[List[Tuple[int
             return False
         if h.aggregation in query.dimensions:
             return False
+        if h.aggregation not in aggs and query.post_aggregator(h.aggregation) is not None:
+            if h.value is None:
+                return const(False)
+            if post is None or isinstance(h.value, bool) or not isinstance(h.value, (int, float)):
+                return False
+            i = post.index(h.aggregation, False)
+            lo, hi = having_interval(t, post.out_type(i), h.value)
+            ops.append((N.HAVING_AGG_RANGE, i, lo, hi))
+            return True
         if h.aggregation not in aggs:  # metric is None
             return const(_having_eval(h, Q.Row(0, {})))
         if h.value is None:
@@ -1642,7 +1716,11 @@ def having_program(query: Q.GroupByQuery, dictionary) -> Optional[List[Tuple[int
 
 def postprocess_groupby(query: Q.GroupByQuery, rows: List[Q.Row]) -> List[Q.Row]:
     """A having spec that selects on a LONG-output dimension, or a limit spec that has to sort on one, is
-    refused (UnsupportedQuery): the host rules here are the string dimensions'."""
+    refused (UnsupportedQuery): the host rules here are the string dimensions'. Post-aggregators are computed
+    for every row first (GroupByStrategyV2.mergeResults, GroupByStrategyV2.java:286-300, computes them before
+    postProcess): having and ORDER BY read them like aggregators, under the post-aggregator's comparator."""
+    if query.postAggregations:
+        rows = [Q.Row(r.timestamp, Q.compute_post_aggregations(query, dict(r.event))) for r in rows]
     if query.having is not None:
         for d in _having_dimensions(query.having):
             if query.dimension_type(d) == "LONG":
@@ -1661,6 +1739,10 @@ def postprocess_groupby(query: Q.GroupByQuery, rows: List[Q.Row]) -> List[Q.Row]
         for c in ls.columns:
             if c.dimension in aggs:
                 fn = aggs[c.dimension].compare_key
+                kf = (lambda f, n: lambda r: f(r.event[n]))(fn, c.dimension)
+            elif query.post_aggregator(c.dimension) is not None:
+                prog = Q.compile_post_aggregator(query.aggregations, query.postAggregations, c.dimension, True)
+                fn = (lambda pr: lambda v: Q.post_program_order_key(pr.order, Q.post_value_word(v, pr.out_type)))(prog)
                 kf = (lambda f, n: lambda r: f(r.event[n]))(fn, c.dimension)
             elif c.dimension in dims:
                 sk = O.sort_key(c.dimensionOrder)
