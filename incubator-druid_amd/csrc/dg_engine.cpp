@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "dg_internal.h"
+#include "dg_javatext.h"
 
 static_assert(DG_POST_AGG == dg::PA_AGG && DG_POST_CONST_D == dg::PA_CONST_D && DG_POST_CONST_L == dg::PA_CONST_L &&
                   DG_POST_L2D == dg::PA_L2D && DG_POST_D2L == dg::PA_D2L && DG_POST_ADD == dg::PA_ADD &&
@@ -423,152 +424,6 @@ static int finish_call(CallScratch* cs, hipStream_t st) {
   return DG_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Java string ordering (String.compareTo = UTF-16 code units; GenericIndexed.STRING_STRATEGY is
-// naturalNullsFirst) and dictionary search (GenericIndexed.indexOf, GenericIndexed.java:308-333)
-// ------------------------------------------------------------------------------------------------
-static void to_utf16(const std::string& s, std::vector<uint16_t>* out) {
-  out->clear();
-  for (size_t i = 0; i < s.size();) {
-    uint32_t c = (uint8_t)s[i];
-    int n = c < 0x80 ? 1 : c < 0xE0 ? 2 : c < 0xF0 ? 3 : 4;
-    if (n == 2) c &= 0x1F;
-    else if (n == 3) c &= 0x0F;
-    else if (n == 4) c &= 0x07;
-    for (int k = 1; k < n && i + k < s.size(); ++k) c = (c << 6) | ((uint8_t)s[i + k] & 0x3F);
-    i += n;
-    if (c >= 0x10000) {
-      c -= 0x10000;
-      out->push_back((uint16_t)(0xD800 + (c >> 10)));
-      out->push_back((uint16_t)(0xDC00 + (c & 0x3FF)));
-    } else {
-      out->push_back((uint16_t)c);
-    }
-  }
-}
-
-static int java_compare(const std::string& a, const std::string& b) {
-  bool ascii = true;
-  for (unsigned char ch : a) ascii &= ch < 0x80;
-  for (unsigned char ch : b) ascii &= ch < 0x80;
-  if (ascii) {
-    int c = a.compare(b);
-    return (c > 0) - (c < 0);
-  }
-  std::vector<uint16_t> ua, ub;
-  to_utf16(a, &ua);
-  to_utf16(b, &ub);
-  size_t n = std::min(ua.size(), ub.size());
-  for (size_t i = 0; i < n; ++i)
-    if (ua[i] != ub[i]) return ua[i] < ub[i] ? -1 : 1;
-  return ua.size() == ub.size() ? 0 : (ua.size() < ub.size() ? -1 : 1);
-}
-
-int java_compare_str(const char* a, const char* b) { return java_compare(std::string(a), std::string(b)); }
-
-// null-aware compare: null < anything
-static int cmp_nullable(bool an, const std::string& a, bool bn, const std::string& b) {
-  if (an || bn) return an == bn ? 0 : (an ? -1 : 1);
-  return java_compare(a, b);
-}
-
-static int index_of(const Column* c, const char* value) {
-  const bool vnull = value == nullptr || value[0] == 0;  // NullHandling.emptyToNullIfNeeded
-  const std::string v = vnull ? std::string() : std::string(value);
-  int lo = 0, hi = (int)c->dict.size() - 1;
-  while (lo <= hi) {
-    int mid = (lo + hi) >> 1;
-    int r = cmp_nullable(c->dict_null[mid], c->dict[mid], vnull, v);
-    if (r == 0) return mid;
-    if (r < 0) lo = mid + 1;
-    else hi = mid - 1;
-  }
-  return -(lo + 1);
-}
-
-// StringComparators.NumericComparator (query/ordering/StringComparators.java:346-392)
-static bool try_long(const char* s, long long* out) {
-  if (!s || !*s) return false;
-  const char* p = s;
-  if (*p == '-') p++;
-  if (!*p) return false;
-  for (const char* q = p; *q; ++q)
-    if (*q < '0' || *q > '9') return false;
-  errno = 0;
-  char* end;
-  long long v = strtoll(s, &end, 10);
-  if (errno || *end) return false;
-  *out = v;
-  return true;
-}
-
-static bool try_decimal(const char* s, long double* out) {
-  if (!s || !*s) return false;
-  // BigDecimal grammar: [+-]digits[.digits][(e|E)[+-]digits] or [+-].digits...
-  const char* p = s;
-  if (*p == '+' || *p == '-') p++;
-  bool digits = false;
-  while (*p >= '0' && *p <= '9') p++, digits = true;
-  if (*p == '.') {
-    p++;
-    while (*p >= '0' && *p <= '9') p++, digits = true;
-  }
-  if (!digits) return false;
-  if (*p == 'e' || *p == 'E') {
-    p++;
-    if (*p == '+' || *p == '-') p++;
-    if (!(*p >= '0' && *p <= '9')) return false;
-    while (*p >= '0' && *p <= '9') p++;
-  }
-  if (*p) return false;
-  *out = strtold(s, nullptr);
-  return true;
-}
-
-static int numeric_compare(const char* a, const char* b) {
-  if (a == b) return 0;
-  if (!a) return -1;
-  if (!b) return 1;
-  long long la, lb;
-  bool ha = try_long(a, &la), hb = try_long(b, &lb);
-  if (ha && hb) return (la > lb) - (la < lb);
-  long double da = ha ? (long double)la : 0, db = hb ? (long double)lb : 0;
-  bool pa = ha || try_decimal(a, &da), pb = hb || try_decimal(b, &db);
-  if (pa && pb) return (da > db) - (da < db);
-  if (!pa && !pb) return java_compare(a, b);
-  return pa ? 1 : -1;
-}
-
-// BoundFilter.doesMatch (BoundFilter.java:249-275), default null mode
-static bool bound_matches(const dg_filter& f, const char* value /* NULL = null */) {
-  const bool has_lower = f.lower != nullptr, has_upper = f.upper != nullptr;
-  if (!value) {
-    const bool lower_null = !has_lower || f.lower[0] == 0;
-    const bool upper_null = !has_upper || f.upper[0] == 0;
-    return (!has_lower || (lower_null && !f.lower_strict)) && (!has_upper || !upper_null || !f.upper_strict);
-  }
-  auto cmp = [&](const char* x, const char* y) {
-    if (f.ordering == DG_ORDER_NUMERIC) return numeric_compare(x, y);
-    return cmp_nullable(x == nullptr, x ? x : "", y == nullptr, y ? y : "");
-  };
-  const int lc = has_lower ? cmp(value, f.lower) : 1;
-  const int uc = has_upper ? cmp(f.upper, value) : 1;
-  if (f.lower_strict && f.upper_strict) return lc > 0 && uc > 0;
-  if (f.lower_strict) return lc > 0 && uc >= 0;
-  if (f.upper_strict) return lc >= 0 && uc > 0;
-  return lc >= 0 && uc >= 0;
-}
-
-static bool leaf_matches_null(const dg_filter& f) {
-  if (f.kind == DG_F_SELECTOR) return f.n_values < 1 || !f.values || !f.values[0] || !f.values[0][0];
-  if (f.kind == DG_F_IN) {
-    for (int i = 0; i < f.n_values; ++i)
-      if (!f.values[i] || !f.values[i][0]) return true;
-    return false;
-  }
-  return bound_matches(f, nullptr);
-}
-
 struct DecodeBatch {
   std::vector<Lz4Job> jobs;
   std::vector<LzfJob> lzf_jobs;  // LZF blocks, decoded one wave per block
@@ -629,437 +484,6 @@ static int build_num_dim(Context* ctx, CallScratch* cs, Segment* seg, Column* c,
 static int run_decodes(CallScratch* cs, DecodeBatch* db, hipStream_t st, uint64_t* d_prof = nullptr, bool overlap = false);
 static int run_decodes_only(CallScratch* cs, DecodeBatch* db, hipStream_t st, uint64_t* d_prof, bool overlap = false);
 
-// ------------------------------------------------------------------------------------------------
-// numeric post-filters: Java's parsing of the filter's strings (host side, once per call)
-// ------------------------------------------------------------------------------------------------
-// java.math.BigDecimal(String) (sign, digits with one optional '.', optional [eE][+-]digits; no
-// whitespace): value = (neg ? -1 : 1) * digits * 10^exp, digits without leading zeros
-struct Decimal {
-  bool neg = false;
-  std::string digits;  // "" = zero
-  long long exp = 0;
-};
-
-static bool parse_big_decimal(const char* s, Decimal* d) {
-  if (!s || !*s) return false;
-  const char* p = s;
-  d->neg = false;
-  if (*p == '+' || *p == '-') d->neg = *p++ == '-';
-  std::string all;
-  long long frac = 0;
-  bool dot = false, any = false;
-  for (; *p; ++p) {
-    if (*p >= '0' && *p <= '9') {
-      all.push_back(*p);
-      any = true;
-      if (dot) frac++;
-    } else if (*p == '.' && !dot) {
-      dot = true;
-    } else {
-      break;
-    }
-  }
-  if (!any) return false;
-  long long e = 0;
-  if (*p == 'e' || *p == 'E') {
-    p++;
-    bool eneg = false;
-    if (*p == '+' || *p == '-') eneg = *p++ == '-';
-    if (!(*p >= '0' && *p <= '9')) return false;
-    for (; *p >= '0' && *p <= '9'; ++p) {
-      e = e * 10 + (*p - '0');
-      if (e > 1000000000ll) return false;  // BigDecimal: the exponent must fit an int
-    }
-    if (eneg) e = -e;
-  }
-  if (*p) return false;
-  size_t z = 0;
-  while (z < all.size() && all[z] == '0') z++;
-  d->digits = all.substr(z);
-  d->exp = e - frac;
-  if (d->digits.empty()) d->neg = false;
-  return true;
-}
-
-// setScale(0, FLOOR / CEILING) (or exact: integral only) then longValueExact. Returns 1 = fits
-// *out, 0 = not integral (exact mode), +2 / -2 = beyond Long.MAX / Long.MIN
-static int decimal_to_long(const Decimal& d, int mode /* 0 exact, 1 floor, 2 ceiling */, long long* out) {
-  std::string ip;  // integer part digits
-  bool frac_nonzero = false;
-  if (d.exp >= 0) {
-    if (!d.digits.empty()) {
-      if (d.digits.size() + (size_t)d.exp > 40) return d.neg ? -2 : 2;
-      ip = d.digits + std::string((size_t)d.exp, '0');
-    }
-  } else {
-    const long long k = -d.exp;
-    if ((long long)d.digits.size() > k) ip = d.digits.substr(0, d.digits.size() - (size_t)k);
-    const std::string fr = (long long)d.digits.size() > k ? d.digits.substr(d.digits.size() - (size_t)k) : d.digits;
-    for (char c : fr) frac_nonzero |= c != '0';
-  }
-  if (mode == 0 && frac_nonzero) return 0;
-  if (ip.size() > 20) return d.neg ? -2 : 2;
-  unsigned __int128 m = 0;
-  for (char c : ip) m = m * 10 + (unsigned)(c - '0');
-  __int128 v = d.neg ? -(__int128)m : (__int128)m;
-  if (frac_nonzero) {
-    if (mode == 1 && d.neg) v -= 1;   // floor of a negative non-integer
-    if (mode == 2 && !d.neg) v += 1;  // ceiling of a positive non-integer
-  }
-  if (v > (__int128)INT64_MAX) return 2;
-  if (v < (__int128)INT64_MIN) return -2;
-  *out = (long long)v;
-  return 1;
-}
-
-// GuavaUtils.tryParseLong (a leading '+' stripped) -> Longs.tryParse: [-]digits within range
-static bool guava_try_parse_long(const char* s, long long* out) {
-  if (!s || !*s) return false;
-  if (*s == '+') s++;
-  return try_long(s, out);
-}
-
-// DimensionHandlerUtils.getExactLongFromDecimalString (DimensionHandlerUtils.java:404-426)
-static bool exact_long(const char* s, long long* out) {
-  if (guava_try_parse_long(s, out)) return true;
-  Decimal d;
-  if (!parse_big_decimal(s, &d)) return false;
-  return decimal_to_long(d, 0, out) == 1;
-}
-
-// Guava Floats/Doubles.tryParse: [+-]?(NaN|Infinity|decimal[eE..]?[fFdD]?|0[xX]hex[pP]exp[fFdD]?)
-// validated like FLOATING_POINT_PATTERN, then Float.parseFloat / Double.parseDouble (correctly rounded)
-static bool guava_float_syntax(const char* s, std::string* body) {
-  if (!s || !*s) return false;
-  const char* p = s;
-  std::string out;
-  if (*p == '+' || *p == '-') out.push_back(*p++);
-  if (!strcmp(p, "NaN") || !strcmp(p, "Infinity")) {
-    *body = out + p;
-    return true;
-  }
-  auto isx = [](char c) { return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'f') || (c >= 'A' && c <= 'F'); };
-  const char* q = p;
-  if (q[0] == '0' && (q[1] == 'x' || q[1] == 'X')) {
-    q += 2;
-    bool any = false;
-    while (isx(*q)) q++, any = true;
-    if (*q == '.') {
-      q++;
-      while (isx(*q)) q++, any = true;
-    }
-    if (!any || (*q != 'p' && *q != 'P')) return false;
-    q++;
-    if (*q == '+' || *q == '-') q++;
-    if (!(*q >= '0' && *q <= '9')) return false;
-    while (*q >= '0' && *q <= '9') q++;
-  } else {
-    bool any = false;
-    while (*q >= '0' && *q <= '9') q++, any = true;
-    if (*q == '.') {
-      q++;
-      while (*q >= '0' && *q <= '9') q++, any = true;
-    }
-    if (!any) return false;
-    if (*q == 'e' || *q == 'E') {
-      q++;
-      if (*q == '+' || *q == '-') q++;
-      if (!(*q >= '0' && *q <= '9')) return false;
-      while (*q >= '0' && *q <= '9') q++;
-    }
-  }
-  out.append(p, q);
-  if (*q == 'f' || *q == 'F' || *q == 'd' || *q == 'D') q++;
-  if (*q) return false;
-  *body = out;
-  return true;
-}
-
-static bool guava_try_parse_double(const char* s, double* out) {
-  std::string b;
-  if (!guava_float_syntax(s, &b)) return false;
-  *out = strtod(b.c_str(), nullptr);
-  return true;
-}
-
-static bool guava_try_parse_float(const char* s, float* out) {
-  std::string b;
-  if (!guava_float_syntax(s, &b)) return false;
-  *out = strtof(b.c_str(), nullptr);
-  return true;
-}
-
-static int64_t float_bits(float f) {  // Float.floatToIntBits
-  if (f != f) return 0x7fc00000ll;
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  return (int64_t)u;
-}
-
-static int64_t double_bits(double d) {  // Double.doubleToLongBits
-  if (d != d) return 0x7ff8000000000000ll;
-  int64_t u;
-  memcpy(&u, &d, 8);
-  return u;
-}
-
-static uint64_t dcmp_key_host(double d) {  // Double.compare order as unsigned keys
-  if (d != d) return ~0ull;
-  uint64_t u;
-  memcpy(&u, &d, 8);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
-struct PredLeaf {
-  NumPred p;
-  std::vector<int64_t> set;
-  std::string lo, hi;
-  const Column* col;
-};
-
-// The row predicate of a selector / in / bound filter on a numeric column, as the reference builds
-// its ValueMatcher. Default null mode: a numeric row is never null, so null-matching predicates
-// (nullValueMatcher) select nothing.
-static int plan_numeric_leaf(const dg_filter& f, const Column* c, PredLeaf* L) {
-  memset(&L->p, 0, sizeof L->p);
-  L->col = c;
-  NumPred& p = L->p;
-  p.kind = PRED_FALSE;
-  const bool is_long = c->type == DG_COL_LONG, is_float = c->type == DG_COL_FLOAT;
-  auto add_value = [&](const char* v) {  // one selector / IN value
-    if (!v || !*v) return;  // emptyToNullIfNeeded -> null: no numeric row matches
-    if (is_long) {
-      long long x;
-      if (exact_long(v, &x)) L->set.push_back(x);
-    } else if (is_float) {
-      float x;
-      if (guava_try_parse_float(v, &x)) L->set.push_back(float_bits(x));
-    } else {
-      double x;
-      if (guava_try_parse_double(v, &x)) L->set.push_back(double_bits(x));
-    }
-  };
-  if (f.kind == DG_F_SELECTOR || f.kind == DG_F_IN) {
-    // SelectorFilter -> {Long,Float,Double}ValueMatcherColumnSelectorStrategy.makeValueMatcher(value)
-    // (convertObjectToLong = getExactLongFromDecimalString, Floats/Doubles.tryParse + *ToIntBits);
-    // InFilter -> InDimFilter.get{Long,Float,Double}PredicateSupplier (the same parsing, a set)
-    const int nv = f.kind == DG_F_SELECTOR ? std::min(f.n_values, 1) : f.n_values;
-    for (int k = 0; k < nv; ++k) add_value(f.values ? f.values[k] : nullptr);
-    std::sort(L->set.begin(), L->set.end());
-    L->set.erase(std::unique(L->set.begin(), L->set.end()), L->set.end());
-    if (!L->set.empty()) p.kind = is_long ? PRED_LONG_SET : PRED_BITS_SET;
-    return DG_OK;
-  }
-  // BoundFilter: NUMERIC ordering -> BoundDimFilter.{long,float,double}PredicateSupplier
-  // (BoundDimFilter.java:341-652); other orderings compare String.valueOf(value) (BoundFilter
-  // makeLongPredicate etc.: doesMatch) — for long columns under LEXICOGRAPHIC (UTF-8 bytes)
-  // the bounds are kept as given (BoundDimFilter.java:73-76; hasLowerBound = lower != null): "" is a
-  // bound, unparseable as a number
-  const char* lo = f.lower;
-  const char* hi = f.upper;
-  p.lo_strict = f.lower_strict;
-  p.hi_strict = f.upper_strict;
-  if (f.ordering != DG_ORDER_NUMERIC) {
-    if (!is_long || f.ordering != DG_ORDER_LEXICOGRAPHIC)
-      return set_error(DG_ERR_UNSUPPORTED, "bound ordering %d on numeric column %s (String.valueOf formatting)",
-                       f.ordering, c->name.c_str());
-    p.kind = PRED_LONG_LEX;
-    p.has_lo = lo != nullptr;
-    p.has_hi = hi != nullptr;
-    L->lo = lo ? lo : "";
-    L->hi = hi ? hi : "";
-    return DG_OK;
-  }
-  if (is_long) {
-    bool nothing = false;
-    long long lv = 0, hv = 0;
-    if (lo) {
-      if (guava_try_parse_long(lo, &lv)) {
-        p.has_lo = 1;
-      } else {
-        Decimal d;
-        if (!parse_big_decimal(lo, &d)) {
-          p.has_lo = 0;  // unparseable: below every number
-        } else {
-          const int r = decimal_to_long(d, f.lower_strict ? 1 : 2, &lv);
-          if (r == 1) p.has_lo = 1;
-          else if (r == 2) nothing = true;  // positive lower bound above every long
-        }
-      }
-    }
-    if (hi) {
-      if (guava_try_parse_long(hi, &hv)) {
-        p.has_hi = 1;
-      } else {
-        Decimal d;
-        if (!parse_big_decimal(hi, &d)) {
-          nothing = true;  // unparseable upper bound: below every number
-        } else {
-          const int r = decimal_to_long(d, f.upper_strict ? 2 : 1, &hv);
-          if (r == 1) p.has_hi = 1;
-          else if (r == -2) nothing = true;
-        }
-      }
-    }
-    p.kind = nothing ? PRED_FALSE : PRED_LONG_RANGE;
-    p.lo = lv;
-    p.hi = hv;
-    return DG_OK;
-  }
-  bool nothing = false;
-  double lv = 0, hv = 0;
-  if (lo) {
-    if (is_float) {
-      float x;
-      p.has_lo = guava_try_parse_float(lo, &x);
-      lv = x;
-    } else {
-      p.has_lo = guava_try_parse_double(lo, &lv);
-    }
-  }
-  if (hi) {
-    bool ok;
-    if (is_float) {
-      float x;
-      ok = guava_try_parse_float(hi, &x);
-      hv = x;
-    } else {
-      ok = guava_try_parse_double(hi, &hv);
-    }
-    p.has_hi = ok;
-    nothing = !ok;
-  }
-  p.kind = nothing ? PRED_FALSE : PRED_ORD_RANGE;
-  p.lo = (int64_t)dcmp_key_host(lv);
-  p.hi = (int64_t)dcmp_key_host(hv);
-  return DG_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// filter planning: prefix nodes -> postfix program over leaf bitsets
-// ------------------------------------------------------------------------------------------------
-struct FilterPlan {
-  std::vector<int32_t> prog;
-  std::vector<std::vector<int32_t>> leaf_ids;  // dictionary ids whose bitmaps are OR-ed
-  std::vector<const Column*> leaf_col;         // null: a row-predicate leaf (leaf_pred)
-  std::vector<int32_t> leaf_pred;              // index into preds, -1 for bitmap leaves
-  std::vector<PredLeaf> preds;
-};
-
-static int plan_node(const Segment* seg, const dg_filter* nodes, int n, int* pos, FilterPlan* fp) {
-  if (*pos >= n) return set_error(DG_ERR_ARG, "truncated filter");
-  const dg_filter& f = nodes[(*pos)++];
-  switch (f.kind) {
-    case DG_F_AND:
-    case DG_F_OR: {
-      if (f.n_children < 1) return set_error(DG_ERR_ARG, "empty and/or filter");
-      for (int c = 0; c < f.n_children; ++c) {
-        int rc = plan_node(seg, nodes, n, pos, fp);
-        if (rc) return rc;
-        if (c > 0) fp->prog.push_back(f.kind == DG_F_AND ? -3 : -4);
-      }
-      return DG_OK;
-    }
-    case DG_F_NOT: {
-      int rc = plan_node(seg, nodes, n, pos, fp);
-      if (rc) return rc;
-      fp->prog.push_back(-5);
-      return DG_OK;
-    }
-    case DG_F_SELECTOR:
-    case DG_F_IN:
-    case DG_F_BOUND: {
-      if (!f.dimension) return set_error(DG_ERR_ARG, "filter without dimension");
-      const Column* c = seg->find(f.dimension);
-      if (!c) {
-        // missing column: allTrue iff the filter matches null (ColumnSelectorBitmapIndexSelector.java:212-218)
-        fp->prog.push_back(leaf_matches_null(f) ? -1 : -2);
-        return DG_OK;
-      }
-      if (c->type == DG_COL_LONG || c->type == DG_COL_FLOAT || c->type == DG_COL_DOUBLE) {
-        // no bitmap index: a row post-filter (QueryableIndexStorageAdapter.java:244-260, FilteredOffset)
-        PredLeaf L;
-        int rc = plan_numeric_leaf(f, c, &L);
-        if (rc) return rc;
-        if (L.p.kind == PRED_FALSE) {
-          fp->prog.push_back(-2);
-          return DG_OK;
-        }
-        fp->prog.push_back((int32_t)fp->leaf_ids.size());
-        fp->leaf_ids.emplace_back();
-        fp->leaf_col.push_back(nullptr);
-        fp->leaf_pred.push_back((int32_t)fp->preds.size());
-        fp->preds.push_back(std::move(L));
-        return DG_OK;
-      }
-      if (c->type != DG_COL_STRING)
-        return set_error(DG_ERR_UNSUPPORTED, "filter on %s needs a bitmap index", f.dimension);
-      std::vector<int32_t> ids;
-      if (f.kind == DG_F_SELECTOR) {
-        int i = index_of(c, f.n_values > 0 && f.values ? f.values[0] : nullptr);
-        if (i >= 0) ids.push_back(i);
-      } else if (f.kind == DG_F_IN) {
-        for (int k = 0; k < f.n_values; ++k) {
-          int i = index_of(c, f.values[k]);
-          if (i >= 0) ids.push_back(i);
-        }
-        std::sort(ids.begin(), ids.end());
-        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-      } else if (f.ordering == DG_ORDER_LEXICOGRAPHIC) {
-        // BoundFilter.getStartEndIndexes (BoundFilter.java:141-174)
-        const int card = (int)c->dict.size();
-        int start, end;
-        if (!f.lower) start = 0;
-        else {
-          int found = index_of(c, f.lower);
-          start = found >= 0 ? (f.lower_strict ? found + 1 : found) : -(found + 1);
-        }
-        if (!f.upper) end = card;
-        else {
-          int found = index_of(c, f.upper);
-          end = found >= 0 ? (f.upper_strict ? found : found + 1) : -(found + 1);
-        }
-        if (end < start) end = start;
-        for (int i = start; i < end; ++i) ids.push_back(i);
-      } else if (f.ordering == DG_ORDER_NUMERIC) {
-        // predicate over every dictionary value (Filters.matchPredicate, Filters.java:239-290)
-        for (int i = 0; i < (int)c->dict.size(); ++i)
-          if (bound_matches(f, c->dict_null[i] ? nullptr : c->dict[i].c_str())) ids.push_back(i);
-      } else {
-        return set_error(DG_ERR_UNSUPPORTED, "bound ordering %d", f.ordering);
-      }
-      if (ids.empty()) {
-        fp->prog.push_back(-2);
-        return DG_OK;
-      }
-      if (!c->has_bitmaps) {
-        // no bitmap index (an in-memory segment): the matching ids become a row predicate, as
-        // IncrementalIndexStorageAdapter's cursors evaluate filter.makeMatcher per row
-        PredLeaf L;
-        memset(&L.p, 0, sizeof L.p);
-        L.p.kind = PRED_ID_SET;
-        L.col = c;
-        L.set.assign((c->dict.size() + 63) / 64, 0);
-        for (int32_t i : ids) L.set[i >> 6] |= (int64_t)(1ull << (i & 63));
-        L.p.has_lo = c->multi_value && !c->dict.empty() && c->dict_null[0] && !ids.empty() && ids[0] == 0;
-        fp->prog.push_back((int32_t)fp->leaf_ids.size());
-        fp->leaf_ids.emplace_back();
-        fp->leaf_col.push_back(nullptr);
-        fp->leaf_pred.push_back((int32_t)fp->preds.size());
-        fp->preds.push_back(std::move(L));
-        return DG_OK;
-      }
-      fp->prog.push_back((int32_t)fp->leaf_ids.size());
-      fp->leaf_ids.push_back(std::move(ids));
-      fp->leaf_col.push_back(c);
-      fp->leaf_pred.push_back(-1);
-      return DG_OK;
-    }
-    default:
-      return set_error(DG_ERR_ARG, "unknown filter kind %d", f.kind);
-  }
-}
-
 // Build the row bitset of `filter` for segment `seg` on the device. *out = nullptr means "all rows".
 // The bitset's cardinality lands in the pinned word *count once finish_call has synchronised
 // (nullptr when there is no filter: every row). Nothing here synchronises.
@@ -1068,20 +492,11 @@ static int build_bitset(Segment* seg, CallScratch* cs, const dg_filter* filter, 
   *out = nullptr;
   *count = nullptr;
   if (!filter || n_filter <= 0) return DG_OK;
-  FilterPlan fp;
-  int pos = 0;
-  int rc = plan_node(seg, filter, n_filter, &pos, &fp);
+  FilterPlan fp;  // (dg_filter_plan.cpp)
+  int rc = plan_filter(
+      [](const void* s, const char* name) -> const DictColumn* { return static_cast<const Segment*>(s)->find(name); },
+      seg, filter, n_filter, &fp);
   if (rc) return rc;
-  if (pos != n_filter) return set_error(DG_ERR_ARG, "filter has %d trailing nodes", n_filter - pos);
-  if (fp.prog.size() > 64) return set_error(DG_ERR_UNSUPPORTED, "filter program too long");
-  // stack depth check (kernel stack of 16)
-  int depth = 0, maxd = 0;
-  for (int op : fp.prog) {
-    if (op >= -2) depth++;
-    else if (op != -5) depth--;
-    maxd = std::max(maxd, depth);
-  }
-  if (maxd > 16) return set_error(DG_ERR_UNSUPPORTED, "filter nesting too deep");
   const int64_t nwords = (seg->nrows + 31) / 32;
   const int nleaves = (int)fp.leaf_ids.size();
   // the program and the row count staged first: the leaves' upload carries them
@@ -1105,7 +520,7 @@ static int build_bitset(Segment* seg, CallScratch* cs, const dg_filter* filter, 
   DG_HIP(hipMemsetAsync(leaf_mem, 0, (size_t)std::max(nleaves, 1) * (nwords + 2) * 4, st));
   // one launch per (column, codec): group leaves by column
   for (int l = 0; l < nleaves; ++l) {
-    const Column* c = fp.leaf_col[l];
+    const Column* c = static_cast<const Column*>(fp.leaf_col[l]);
     if (!c) continue;  // row-predicate leaf, below
     // gather all leaves on the same column into this launch
     bool first = true;
@@ -1191,7 +606,8 @@ static int build_bitset(Segment* seg, CallScratch* cs, const dg_filter* filter, 
     ColView v, voff;
     memset(&v, 0, sizeof v);
     memset(&voff, 0, sizeof voff);
-    int rc2 = L.col->multi_value ? multi_view(L.col, cs, &db, &v, &voff, st) : column_view(L.col, cs, &db, &v, st);
+    const Column* col = static_cast<const Column*>(L.col);
+    int rc2 = col->multi_value ? multi_view(col, cs, &db, &v, &voff, st) : column_view(col, cs, &db, &v, st);
     if (rc2) return rc2;
     if (!L.set.empty()) {
       int64_t* d_set;

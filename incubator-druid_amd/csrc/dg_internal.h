@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/druidgpu.h"
+#include "dg_filter_plan.h"
 #include "dg_postagg.h"
 
 namespace dg {
@@ -415,18 +416,13 @@ constexpr int kRoaringSplitBytes = 32768; // Roaring bitmaps above this are cut 
 
 constexpr int kOrderSlots = 8;
 
-struct Column {
-  std::string name;
-  int type = DG_COL_MISSING;
+// (name, type, dict, dict_null, has_bitmaps and multi_value: DictColumn, what the filter planner reads)
+struct Column : DictColumn {
   BlockColumn data;
-  // dictionary-encoded string column
-  std::vector<std::string> dict;
-  std::vector<uint8_t> dict_null;      // 1 = null / empty value
   std::vector<uint64_t> dict_hash;     // value_hash of every dictionary value (cross-segment merges)
   int bitmap_roaring = 0;
-  bool has_bitmaps = false;
-  bool multi_value = false;            // row r's values: data[mv_off[r] .. mv_off[r + 1])
-  BlockColumn mv_off;                  // multi-value: rows + 1 value offsets (4-byte ints)
+  BlockColumn mv_off;                  // multi_value: rows + 1 value offsets (4-byte ints); row r's values:
+                                       // data[mv_off[r] .. mv_off[r + 1])
   std::vector<int64_t> bm_off;         // byte offset of each bitmap inside bm_bytes (4-byte aligned)
   std::vector<int32_t> bm_len;
   DevBuf bm_bytes;
@@ -603,8 +599,7 @@ inline uint64_t value_hash(const std::string& v) {
   return h == kNullValueHash ? h + 1 : h;
 }
 
-// error reporting
-int set_error(int code, const char* fmt, ...);
+// error reporting (set_error: declared in dg_filter_plan.h, defined in dg_engine.cpp)
 #define DG_HIP(call)                                                                       \
   do {                                                                                     \
     hipError_t _e = (call);                                                                \
@@ -615,7 +610,6 @@ int set_error(int code, const char* fmt, ...);
 int load_segment(Context* ctx, const char* dir, Segment** out);
 int segment_from_rows(Context* ctx, int64_t nrows, const int64_t* ts, int64_t istart, int64_t iend,
                       const dg_row_column* cols, int ncols, Segment** out);
-int java_compare_str(const char* a, const char* b);  // String.compareTo over UTF-8 bytes (dg_engine.cpp)
 
 // a failed enqueue inside a void launcher (e.g. the memset of look-back status): recorded per thread,
 // returned as DG_ERR_DEVICE by the call's finish_call (dg_engine.cpp)
@@ -786,29 +780,7 @@ struct FlResolveJob {
   int32_t okind[kMaxAggs];  // DG_AGG_LONG_SUM / DOUBLE_SUM / FLOAT_SUM: the value's type
 };
 void launch_fl_resolve(const FlResolveJob* d_jobs, int njobs, int64_t max_pairs, hipStream_t s);
-// Row predicate of a filter on a numeric column: the reference evaluates it per row as a post-filter
-// (QueryableIndexStorageAdapter.makeCursors :244-260 -> FilteredOffset.java:40-105) through the
-// column's ValueMatcher ({Long,Float,Double}ValueMatcherColumnSelectorStrategy, the filters'
-// DruidLong/Float/DoublePredicate); here it becomes one more row bitset of the filter program.
-enum PredKind : int32_t {
-  PRED_FALSE = 0,       // matches no row (unparseable selector value, empty IN, ALWAYS_FALSE bounds)
-  PRED_LONG_RANGE = 1,  // long column: [lo, hi] with strictness (makeLongPredicateFromBounds)
-  PRED_LONG_SET = 2,    // long column: value in the sorted set (IN / selector)
-  PRED_ORD_RANGE = 3,   // float/double column: Double.compare range on (double) value, as ordered keys
-  PRED_BITS_SET = 4,    // float/double column: floatToIntBits / doubleToLongBits in the sorted set
-  PRED_LONG_LEX = 5,    // long column: String.valueOf(value) vs UTF-8 bound strings (LEXICOGRAPHIC)
-  PRED_ID_SET = 6,      // string column without a bitmap index: row id's bit in `set` (64-bit words)
-};
-struct NumPred {
-  int32_t kind;
-  int32_t has_lo, has_hi, lo_strict, hi_strict;
-  int32_t nset;
-  int64_t lo, hi;         // LONG_RANGE: bounds; ORD_RANGE: ordered keys (uint64 bit patterns)
-  const int64_t* set;     // LONG_SET / BITS_SET: sorted values / canonical bit patterns
-  const uint8_t* lo_str;  // LONG_LEX: bound bytes
-  const uint8_t* hi_str;
-  int32_t lo_len, hi_len;
-};
+// The row predicate of a filter leaf without a bitmap index (NumPred, dg_filter_plan.h) over a column:
 // out: bitset words of rows [0, nrows) (bit r of word r >> 5); v: the decoded numeric column
 // voff: row value offsets of a multi-value id column (VIEW_ABSENT otherwise); PRED_ID_SET over a
 // multi-value column: has_lo = whether an empty row (the null value) matches

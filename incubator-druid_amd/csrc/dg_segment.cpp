@@ -32,6 +32,7 @@
 #include <thread>
 
 #include "dg_internal.h"
+#include "dg_javatext.h"
 
 namespace dg {
 
@@ -1367,7 +1368,7 @@ int segment_from_rows(Context* ctx, int64_t nrows, const int64_t* ts, int64_t is
       std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
         const bool an = is_null(a), bn = is_null(b);
         if (an || bn) return an && !bn;
-        return java_compare_str(rc_.dict[a], rc_.dict[b]) < 0;
+        return java_compare(rc_.dict[a], rc_.dict[b]) < 0;
       });
       std::vector<int32_t> remap(card);
       for (int32_t k = 0; k < card; ++k) {

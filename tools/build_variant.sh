@@ -10,6 +10,7 @@ $H -c -x hip dg_lz4.hip -o $out/obj/dg_lz4.o &
 $H -c -x hip dg_kernels.hip -o $out/obj/dg_kernels.o &
 $H -c -x hip dg_sort.hip -o $out/obj/dg_sort.o &
 $H -c dg_engine.cpp -o $out/obj/dg_engine.o &
+$H -c dg_filter_plan.cpp -o $out/obj/dg_filter_plan.o &
 $H -c dg_segment.cpp -o $out/obj/dg_segment.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libdruidgpu.so $out/obj/*.o
