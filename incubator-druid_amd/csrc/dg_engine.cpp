@@ -418,6 +418,7 @@ static int finish_call(CallScratch* cs, hipStream_t st) {
   if (cs->d_err && (*cs->h_err & kErrTableFull)) return set_error(DG_ERR_TABLE_FULL, "groupBy hash table full");
   if (cs->d_err && *cs->h_err)
     return set_error(DG_ERR_FORMAT, (*cs->h_err & 1)            ? "corrupt LZ4 block"
+                                    : (*cs->h_err & kErrLzf)    ? "corrupt LZF block"
                                     : (*cs->h_err & 4)          ? "corrupt multi-value row lists"
                                     : (*cs->h_err & kErrDictId) ? "dictionary id outside its dictionary"
                                                                 : "corrupt Roaring bitmap");

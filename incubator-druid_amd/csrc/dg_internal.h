@@ -923,6 +923,7 @@ struct CountTotals {
   uint32_t n;     // elements of the call (stored to sb->n[0] by the totals kernel)
 };
 constexpr int32_t kErrDictId = 16;  // bit of the call's device error word: a dictionary id >= its cardinality
+constexpr int32_t kErrLzf = 32;     // bit of the call's device error word: k_lzf_decode refused a block
 // bits of the first digit of a sort over key_bits key bits (0: no pass), and its passes
 int radix_first_digit_bits(int key_bits);
 int radix_pass_count(int key_bits);

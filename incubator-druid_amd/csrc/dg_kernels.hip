@@ -1835,7 +1835,7 @@ __global__ __launch_bounds__(64) void k_lzf_decode(const LzfJob* __restrict__ jo
   }
   __syncthreads();
   if (bad || op < j.expect_len) {
-    if (lane == 0) atomicOr(err, 1);
+    if (lane == 0) atomicOr(err, kErrLzf);
     return;
   }
   const int o16 = op >> 4;

@@ -132,19 +132,20 @@ def max_ints_in_buffer_for_bytes(num_bytes: int) -> int:
 # --------------------------------------------------------------------------------------------
 # Column part serializers
 # --------------------------------------------------------------------------------------------
-def _compress_blocks(raw: bytes, block_bytes: int, compression: str, lz4_mode: str) -> List[bytes]:
-    blocks = []
-    for off in range(0, len(raw), block_bytes):
-        chunk = raw[off:off + block_bytes]
-        if compression == "lz4":
-            blocks.append(lz4_compress(chunk, lz4_mode))
-        elif compression == "lzf":
-            blocks.append(_tools.lzf_compress(chunk))
-        elif compression == "uncompressed":
-            blocks.append(chunk)
-        else:
-            raise ValueError(f"unsupported block compression {compression}")
-    return blocks
+def _compress_block(chunk: bytes, compression: str, lz4_mode: str, lzf_encoder=None) -> bytes:
+    """One block of a block-layout column in its stored form. lzf_encoder: see write_segment."""
+    if compression == "lz4":
+        return lz4_compress(chunk, lz4_mode)
+    if compression == "lzf":
+        return _tools.lzf_compress(chunk) if lzf_encoder is None else bytes(lzf_encoder(bytes(chunk)))
+    if compression == "uncompressed":
+        return chunk
+    raise ValueError(f"unsupported block compression {compression}")
+
+
+def _compress_blocks(raw: bytes, block_bytes: int, compression: str, lz4_mode: str, lzf_encoder=None) -> List[bytes]:
+    return [_compress_block(raw[off:off + block_bytes], compression, lz4_mode, lzf_encoder)
+            for off in range(0, len(raw), block_bytes)]
 
 
 VSIZE_SUPPORTED = (1, 2, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64)
@@ -214,7 +215,8 @@ def choose_long_encoding(values: np.ndarray):
     return "longs", None
 
 
-def packed_long_column_part(values: np.ndarray, compression: str, lz4_mode: str, fmt: str, meta) -> bytes:
+def packed_long_column_part(values: np.ndarray, compression: str, lz4_mode: str, fmt: str, meta,
+                            lzf_encoder=None) -> bytes:
     """BlockLayout / EntireLayout long column with a DELTA or TABLE LongEncodingWriter:
     [0x02][i32 total][i32 sizePer][cid - 126 (encoding flag)][format id][encoding meta][blocks]
     (BlockLayoutColumnarLongsSerializer.java:37-41,60-66; DeltaLongEncodingWriter.putMeta :59-66;
@@ -231,28 +233,20 @@ def packed_long_column_part(values: np.ndarray, compression: str, lz4_mode: str,
     if compression == "none":  # EntireLayoutColumnarLongsSerializer writes sizePer 0 (:35-39)
         return struct.pack(">Bii", 0x02, n, 0) + bytes([flagged]) + enc + vsize_pack(packed, bits)
     size_per = vsize_values_per_block(bits)
-    blocks = []
-    for off in range(0, n, size_per):
-        chunk = vsize_pack(packed[off:off + size_per], bits)
-        if compression == "lz4":
-            blocks.append(lz4_compress(chunk, lz4_mode))
-        elif compression == "lzf":
-            blocks.append(_tools.lzf_compress(chunk))
-        elif compression == "uncompressed":
-            blocks.append(chunk)
-        else:
-            raise ValueError(f"unsupported block compression {compression}")
+    blocks = [_compress_block(vsize_pack(packed[off:off + size_per], bits), compression, lz4_mode, lzf_encoder)
+              for off in range(0, n, size_per)]
     return struct.pack(">Bii", 0x02, n, size_per) + bytes([flagged]) + enc + _blocks_generic_indexed(blocks)
 
 
 def numeric_column_part(values: np.ndarray, kind: str, compression: str, lz4_mode: str,
-                        long_encoding: str = "longs") -> bytes:
+                        long_encoding: str = "longs", lzf_encoder=None) -> bytes:
     """CompressedColumnar{Longs,Floats,Doubles}Supplier layout, LONGS encoding (legacy, no flag), or
     for longs with long_encoding="auto" the format IntermediateColumnarLongsSerializer picks."""
     if kind == "long" and long_encoding == "auto" and len(values):
         fmt, meta = choose_long_encoding(values)
         if fmt != "longs":
-            return packed_long_column_part(np.asarray(values, dtype=np.int64), compression, lz4_mode, fmt, meta)
+            return packed_long_column_part(np.asarray(values, dtype=np.int64), compression, lz4_mode, fmt, meta,
+                                           lzf_encoder)
     elif long_encoding not in ("longs", "auto"):
         raise ValueError(f"unknown long encoding {long_encoding}")
     dtype = {"long": "<i8", "double": "<f8", "float": "<f4"}[kind]
@@ -263,17 +257,18 @@ def numeric_column_part(values: np.ndarray, kind: str, compression: str, lz4_mod
         # LZF_VERSION (0x01) columns of older segments: no compression byte, LZF blocks
         # (CompressedColumnarLongsSupplier.fromByteBuffer, :102-116)
         return struct.pack(">Bii", 0x01, len(arr), size_per) + \
-            _blocks_generic_indexed(_compress_blocks(arr.tobytes(), size_per * width, "lzf", lz4_mode))
+            _blocks_generic_indexed(_compress_blocks(arr.tobytes(), size_per * width, "lzf", lz4_mode, lzf_encoder))
     cid = COMPRESSION_IDS[compression]
     header = struct.pack(">Bii", 0x02, len(arr), size_per) + bytes([cid])
     raw = arr.tobytes()
     if compression == "none":
         # EntireLayoutColumnar{Longs,...}: values follow directly (CompressionFactory.getLongSupplier)
         return header + raw
-    return header + _blocks_generic_indexed(_compress_blocks(raw, size_per * width, compression, lz4_mode))
+    return header + _blocks_generic_indexed(_compress_blocks(raw, size_per * width, compression, lz4_mode, lzf_encoder))
 
 
-def ids_part(ids: np.ndarray, cardinality: int, compression: str, lz4_mode: str, num_bytes: Optional[int] = None) -> bytes:
+def ids_part(ids: np.ndarray, cardinality: int, compression: str, lz4_mode: str, num_bytes: Optional[int] = None,
+             lzf_encoder=None) -> bytes:
     """CompressedVSizeColumnarIntsSerializer (little-endian values, numBytes from cardinality; num_bytes
     forces a wider id, e.g. the 4-byte form CompressedVSizeColumnarIntsSupplier reads as full ints)."""
     nb = num_bytes or num_bytes_for_max(cardinality)
@@ -286,7 +281,7 @@ def ids_part(ids: np.ndarray, cardinality: int, compression: str, lz4_mode: str,
     cid = COMPRESSION_IDS["uncompressed" if compression == "none" else compression]
     header = struct.pack(">BBii", 0x02, nb, len(ids32), size_per) + bytes([cid])
     comp = "uncompressed" if compression == "none" else compression
-    return header + _blocks_generic_indexed(_compress_blocks(raw, size_per * nb, comp, lz4_mode))
+    return header + _blocks_generic_indexed(_compress_blocks(raw, size_per * nb, comp, lz4_mode, lzf_encoder))
 
 
 def vsize_ids_part(ids: np.ndarray, cardinality: int, num_bytes: Optional[int] = None) -> bytes:
@@ -381,8 +376,9 @@ def encoded_bitmaps(rows_of_value: Sequence[np.ndarray], num_rows: int, bitmap_e
 
 def string_column_part(dictionary: List[Optional[str]], ids: np.ndarray, bitmap: str,
                        compression: str, lz4_mode: str, num_bytes: Optional[int] = None,
-                       bitmap_encoder=None) -> bytes:
-    """bitmap_encoder: see encoded_bitmaps; None writes the canonical Concise / Roaring bytes."""
+                       bitmap_encoder=None, lzf_encoder=None) -> bytes:
+    """bitmap_encoder: see encoded_bitmaps; None writes the canonical Concise / Roaring bytes.
+    lzf_encoder: see write_segment."""
     card = len(dictionary)
     dict_vals = [None if (v is None or v == "") else v.encode("utf-8") for v in dictionary]
     # null / "" are both stored as a zero-length value (NullHandling.replaceWithDefault)
@@ -397,7 +393,7 @@ def string_column_part(dictionary: List[Optional[str]], ids: np.ndarray, bitmap:
     else:
         out = bytes([0x02]) + struct.pack(">i", 0)  # COMPRESSED, flags = 0 (single-value, bitmaps)
         out += generic_indexed(dict_vals, sorted_flag=True)
-        out += ids_part(ids, card, compression, lz4_mode, num_bytes)
+        out += ids_part(ids, card, compression, lz4_mode, num_bytes, lzf_encoder)
     if bitmap_encoder is not None:
         order = np.argsort(ids, kind="stable")
         bounds = np.searchsorted(ids[order], np.arange(card + 1))
@@ -421,7 +417,8 @@ def encode_multi_strings(rows: Sequence[Sequence[Optional[str]]]) -> Tuple[List[
 
 
 def multi_string_column_part(dictionary: List[Optional[str]], rows: Sequence[np.ndarray], bitmap: str,
-                             compression: str, lz4_mode: str, legacy: bool = False, bitmap_encoder=None) -> bytes:
+                             compression: str, lz4_mode: str, legacy: bool = False, bitmap_encoder=None,
+                             lzf_encoder=None) -> bytes:
     """Multi-value dictionary-encoded column (DictionaryEncodedColumnPartSerde.java:183-217):
     compressed = version COMPRESSED + MULTI_VALUE_V3 flag, ids as V3CompressedVSizeColumnarMultiInts
     ([0x03][CompressedColumnarInts row start offsets + end][CompressedVSizeColumnarInts values],
@@ -439,7 +436,8 @@ def multi_string_column_part(dictionary: List[Optional[str]], rows: Sequence[np.
         out = bytes([0x02]) + struct.pack(">i", 0x1) + generic_indexed(dict_vals, sorted_flag=True)
         offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         total = int(offsets[-1])
-        out += bytes([0x02]) + ids_part(offsets, total, bc, lz4_mode) + ids_part(flat, card, bc, lz4_mode)
+        out += bytes([0x02]) + ids_part(offsets, total, bc, lz4_mode, lzf_encoder=lzf_encoder) + \
+            ids_part(flat, card, bc, lz4_mode, lzf_encoder=lzf_encoder)
     elif compression in ("uncompressed", "none"):
         out = bytes([0x01]) + generic_indexed(dict_vals, sorted_flag=True)
         ends = np.cumsum(lens * nb).astype(">i4")
@@ -452,8 +450,8 @@ def multi_string_column_part(dictionary: List[Optional[str]], rows: Sequence[np.
         size_per = BUFFER_SIZE // 4  # CompressedColumnarIntsSupplier.MAX_INTS_IN_BUFFER
         cid = COMPRESSION_IDS[compression]
         out += bytes([0x03]) + struct.pack(">Bii", 0x02, len(offsets), size_per) + bytes([cid])
-        out += _blocks_generic_indexed(_compress_blocks(offsets.tobytes(), size_per * 4, compression, lz4_mode))
-        out += ids_part(flat, card, compression, lz4_mode)
+        out += _blocks_generic_indexed(_compress_blocks(offsets.tobytes(), size_per * 4, compression, lz4_mode, lzf_encoder))
+        out += ids_part(flat, card, compression, lz4_mode, lzf_encoder=lzf_encoder)
     row_of = np.repeat(np.arange(len(rows), dtype=np.int64), lens)
     order = np.lexsort((row_of, flat))
     sf, sr = flat[order], row_of[order]
@@ -528,7 +526,7 @@ class SegmentSpec:
 def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", compression: str = "lz4",
                   dim_compression: Optional[str] = None, lz4_mode: str = "hc", long_encoding: str = "longs",
                   id_bytes: Optional[int] = None, legacy_multi_value: bool = False, check_sorted: bool = True,
-                  bitmap_encoder=None) -> str:
+                  bitmap_encoder=None, lzf_encoder=None) -> str:
     """Write a v9 segment directory. Rows must already be in segment order (time-sorted).
     long_encoding: IndexSpec.longEncoding, "longs" (default) or "auto" (DELTA / TABLE / LONGS per column,
     __time included: IndexMergerV9 serializes it with the same long encoding).
@@ -538,7 +536,10 @@ def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", comp
     never writes such a segment).
     bitmap_encoder: a callable (ascending int64 rows, num_rows) -> bytes that encodes every dictionary
     value's bitmap in place of the canonical encoder (other legal forms of the same rows; see
-    encoded_bitmaps). None: the canonical bytes."""
+    encoded_bitmaps). None: the canonical bytes.
+    lzf_encoder: a callable (block_plaintext: bytes) -> bytes that compresses every LZF block (of __time, the
+    metrics and the dimension ids, under "lzf" and "lzf_v1") in place of the build's encoder: any other legal
+    compress-lzf chunk stream of the same bytes, or on purpose an illegal one. None: the build's encoder."""
     os.makedirs(out_dir, exist_ok=True)
     n = len(spec.timestamps)
     ts = np.asarray(spec.timestamps, dtype=np.int64)
@@ -548,7 +549,7 @@ def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", comp
                                    "lzf" if compression == "lzf_v1" else compression)
     files: Dict[str, bytes] = {}
     files["__time"] = _descriptor("LONG", {"type": "long", "byteOrder": "LITTLE_ENDIAN"}) + \
-        numeric_column_part(ts, "long", compression, lz4_mode, long_encoding)
+        numeric_column_part(ts, "long", compression, lz4_mode, long_encoding, lzf_encoder)
     for name, (dictionary, ids) in spec.dims.items():
         if isinstance(ids, list) and ids and isinstance(ids[0], (list, tuple, np.ndarray)):
             if len(ids) != n:
@@ -557,13 +558,15 @@ def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", comp
                     "byteOrder": "LITTLE_ENDIAN"}
             files[name] = _descriptor("STRING", part, multi=True) + multi_string_column_part(
                 dictionary, [np.asarray(r, dtype=np.int32) for r in ids], bitmap, dim_comp, lz4_mode, legacy_multi_value,
-                bitmap_encoder)
+                bitmap_encoder, lzf_encoder)
             continue
         ids = np.asarray(ids, dtype=np.int32)
         if len(ids) != n:
             raise ValueError(f"dimension {name} has {len(ids)} rows, expected {n}")
         part = {"type": "stringDictionary", "bitmapSerdeFactory": _bitmap_json(bitmap), "byteOrder": "LITTLE_ENDIAN"}
         hook = {} if bitmap_encoder is None else {"bitmap_encoder": bitmap_encoder}
+        if lzf_encoder is not None:
+            hook["lzf_encoder"] = lzf_encoder
         files[name] = _descriptor("STRING", part) + string_column_part(dictionary, ids, bitmap, dim_comp, lz4_mode,
                                                                        id_bytes, **hook)
     for name, (kind, vals) in spec.metrics.items():
@@ -572,7 +575,7 @@ def write_segment(out_dir: str, spec: SegmentSpec, bitmap: str = "concise", comp
             raise ValueError(f"metric {name} has {len(vals)} rows, expected {n}")
         vt = {"long": "LONG", "double": "DOUBLE", "float": "FLOAT"}[kind]
         files[name] = _descriptor(vt, {"type": kind, "byteOrder": "LITTLE_ENDIAN"}) + \
-            numeric_column_part(vals, kind, compression, lz4_mode, long_encoding)
+            numeric_column_part(vals, kind, compression, lz4_mode, long_encoding, lzf_encoder)
     dims = list(spec.dims.keys())
     cols = dims + list(spec.metrics.keys())
     if spec.interval is not None:

@@ -2,7 +2,10 @@
 segments). The codec is compress-lzf 1.0.4 (a pom dependency, not vendored): the oracle restates
 its published chunk format ("ZV" chunks, liblzf tokens) and is pinned by hand-assembled known-answer
 chunks below plus round trips through the writer's encoder; the GPU decoder (k_lzf_decode) is checked
-bit-exact against the oracle on per-row buckets."""
+bit-exact against the oracle on per-row buckets. These are the writer's own streams; other legal streams of
+the format (crafted token by token: every length, distance, overlap, chunk shape and window position), the
+decoded tails of 1..15 bytes and the malformed streams are in lzf_variants.py, test_lzf_variants.py (CPU,
+with a census of what the streams reach) and test_lzf_variants_gpu.py."""
 import importlib
 
 import numpy as np
