@@ -847,6 +847,90 @@ int dg_topn_run_post(dg_segment* const* segs, int32_t n_segs, const dg_scan* sca
 int dg_topn_merge_post(dg_segment* const* segs, const dg_scan* scan, const dg_topn* topn, const dg_topn_lists* in,
                        const dg_topn_opts* opts, const dg_post_agg* metric, int32_t* out_n, int32_t* out_list,
                        int64_t* out_keys, uint64_t* out_values);
+/* ---- derived columns: numeric expressions ----
+ * ExpressionVirtualColumn, the `expression` of the simple aggregator factories and ExpressionDimFilter
+ * (segment/virtual/ExpressionVirtualColumn.java, SimpleDoubleAggregatorFactory.java:59, ExpressionFilter.java:
+ * 54-66) all evaluate one numeric expression per row. dg_segment_derive_column evaluates it ONCE per segment on
+ * the device (k_expr_eval) into a flat LONG, DOUBLE or FLOAT column in HBM and registers it under `name`; from
+ * then on every call that names the column reads it like a stored one (aggregator inputs, numeric filter leaves,
+ * numeric dimensions, dg_rows_run). It costs 8 bytes per row (FLOAT: 4) of HBM, counted in
+ * dg_segment_device_bytes, until dg_segment_drop_derived or dg_segment_release.
+ *
+ * The expression is a postfix program over up to DG_EXPR_MAX_INPUTS stored numeric columns ("__time" allowed),
+ * compiled and type-checked by the caller. Types are static, long or double; a LONG input pushes the long, a
+ * DOUBLE the double, a FLOAT its exactly widened float32; every NaN is the canonical one.
+ *   DG_EXPR_INPUT arg / CONST_L imm / CONST_D imm (the double's bits)
+ *   DG_EXPR_L2D, DG_EXPR_D2L (Java's saturating cast, NaN -> 0), DG_EXPR_D2F ((float), only as the last op of a
+ *   DG_COL_FLOAT output)
+ *   DG_EXPR_ADD SUB MUL DIV MOD: both operands long (wrapping; MIN / -1 = MIN, MIN % -1 = 0) or both double (IEEE,
+ *   % = fmod), each op rounded on its own           DG_EXPR_NEG, DG_EXPR_NOT (!(x > 0) in the operand's type)
+ *   DG_EXPR_LT LE GT GE (doubles by Double.compare), DG_EXPR_EQ NE (doubles by ==): 1 / 0 in the operands' type
+ *   DG_EXPR_AND / OR: (l > 0 ? r : l) / (l > 0 ? l : r)      DG_EXPR_SELECT: pops c, a, b -> c > 0 ? a : b
+ *   DG_EXPR_ABS, CEIL, FLOOR (doubles), MIN, MAX (Math.min / max), IDIV (long / long, or (long)(x / y))
+ * A long division by zero (the reference throws ArithmeticException for the rows its cursor visits) poisons
+ * the value; a select keeps the poison of its condition and of the branch it chose only. A build that finds
+ * a poisoned row registers nothing and returns DG_ERR_UNSUPPORTED ("division by zero in N rows").
+ *
+ * dg_segment_derive_column is a call on the segment's context like a query (cancel / timeout_ms as in dg_scan).
+ * An identical column (name, program, inputs, type) already there: DG_OK, out->built = 0, nothing runs. Refused
+ * before any launch: DG_ERR_ARG — a program the checker rejects (length, stack, operand types, result type), a
+ * name that is a stored column or a derived column of another program; DG_ERR_UNSUPPORTED — an input the
+ * segment lacks, or a string, multi-value or unsupported one (the reference types those per row). A failed,
+ * cancelled or timed-out build leaves nothing behind.
+ * dg_segment_drop_derived: frees the column and whatever was cached on it (numeric-dimension encoding).
+ * DG_ERR_NOT_FOUND: no such column; DG_ERR_ARG: a stored column. No call may be using the column. */
+#define DG_EXPR_MAX_OPS 64
+#define DG_EXPR_MAX_STACK 16
+#define DG_EXPR_MAX_INPUTS 8
+#define DG_EXPR_INPUT 0
+#define DG_EXPR_CONST_L 1
+#define DG_EXPR_CONST_D 2
+#define DG_EXPR_L2D 3
+#define DG_EXPR_D2L 4
+#define DG_EXPR_D2F 5
+#define DG_EXPR_ADD 6
+#define DG_EXPR_SUB 7
+#define DG_EXPR_MUL 8
+#define DG_EXPR_DIV 9
+#define DG_EXPR_MOD 10
+#define DG_EXPR_NEG 11
+#define DG_EXPR_NOT 12
+#define DG_EXPR_LT 13
+#define DG_EXPR_LE 14
+#define DG_EXPR_GT 15
+#define DG_EXPR_GE 16
+#define DG_EXPR_EQ 17
+#define DG_EXPR_NE 18
+#define DG_EXPR_AND 19
+#define DG_EXPR_OR 20
+#define DG_EXPR_SELECT 21
+#define DG_EXPR_ABS 22
+#define DG_EXPR_CEIL 23
+#define DG_EXPR_FLOOR 24
+#define DG_EXPR_MIN 25
+#define DG_EXPR_MAX 26
+#define DG_EXPR_IDIV 27
+typedef struct {
+  int32_t op;   /* DG_EXPR_* */
+  int32_t arg;  /* DG_EXPR_INPUT: index into `inputs` */
+  uint64_t imm; /* DG_EXPR_CONST_L: the long; DG_EXPR_CONST_D: the double's bits */
+} dg_expr_op;
+typedef struct {
+  const char* const* inputs; /* stored columns of the segment, "__time" allowed */
+  int32_t n_inputs;
+  const dg_expr_op* ops;
+  int32_t n_ops;
+  int32_t out_type; /* DG_COL_LONG / DG_COL_DOUBLE / DG_COL_FLOAT */
+} dg_expr;
+typedef struct {
+  int32_t built; /* 0: an identical column was already there */
+  int32_t type;
+  int64_t rows, device_bytes, poisoned_rows;
+  double build_ms;
+} dg_derived_info;
+int dg_segment_derive_column(dg_segment* seg, const char* name, const dg_expr* expr, const volatile int32_t* cancel,
+                             int64_t timeout_ms, dg_derived_info* out /* may be NULL */);
+int dg_segment_drop_derived(dg_segment* seg, const char* name);
 /* number of merged groups */
 int64_t dg_result_groups(const dg_result* res);
 /* groups [start, start + count), in result order (bucket time, then dimension values in Java

@@ -217,6 +217,36 @@ def make_post_aggs(programs):
     return (dg_post_agg * max(len(cols), 1))(*cols), keep
 
 
+# dg_segment_derive_column: numeric expression programs (the op codes are query.EX_*)
+EXPR_MAX_OPS, EXPR_MAX_STACK, EXPR_MAX_INPUTS = 64, 16, 8
+
+
+class dg_expr_op(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("imm", ctypes.c_uint64)]
+
+
+class dg_expr(ctypes.Structure):
+    _fields_ = [("inputs", ctypes.POINTER(ctypes.c_char_p)), ("n_inputs", ctypes.c_int32),
+                ("ops", ctypes.POINTER(dg_expr_op)), ("n_ops", ctypes.c_int32), ("out_type", ctypes.c_int32)]
+
+
+class dg_derived_info(ctypes.Structure):
+    _fields_ = [("built", ctypes.c_int32), ("type", ctypes.c_int32), ("rows", ctypes.c_int64),
+                ("device_bytes", ctypes.c_int64), ("poisoned_rows", ctypes.c_int64), ("build_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def make_expr(ops, inputs, out_type: int):
+    """[(op, arg, imm)], input column names, DG_COL_* -> (dg_expr, keep-alive list)."""
+    arr = (dg_expr_op * max(len(ops), 1))(*[dg_expr_op(int(o), int(a), int(i) & ((1 << 64) - 1)) for o, a, i in ops])
+    names = (ctypes.c_char_p * max(len(inputs), 1))(*[_b(n) for n in inputs])
+    e = dg_expr(ctypes.cast(names, ctypes.POINTER(ctypes.c_char_p)), len(inputs),
+                ctypes.cast(arr, ctypes.POINTER(dg_expr_op)), len(ops), int(out_type))
+    return e, [arr, names]
+
+
 class dg_keyspace(ctypes.Structure):
     _fields_ = [("n_dims", ctypes.c_int32), ("card", ctypes.c_void_p), ("period_ms", ctypes.c_int64),
                 ("bucket0", ctypes.c_int64), ("n_buckets", ctypes.c_int64), ("universal_time", ctypes.c_int64),
@@ -243,6 +273,7 @@ EXPORTS = [
     "dg_topn_run_opts", "dg_topn_merge_opts", "dg_segment_numeric_dim_values", "dg_segment_numeric_dim_info",
     "dg_result_post_process", "dg_result_post_aggregate", "dg_result_post_values",
     "dg_topn_run_post", "dg_topn_merge_post",
+    "dg_segment_derive_column", "dg_segment_drop_derived",
 ]
 
 _lib = None
@@ -345,6 +376,8 @@ def lib():
                                               P(dg_post_agg), P(i32), vp, vp, vp]),
         "dg_segment_numeric_dim_values": (ctypes.c_int, [vp, cp, vp, i32, vp]),
         "dg_segment_numeric_dim_info": (ctypes.c_int, [vp, cp, P(i32), P(i64), P(i64), P(ctypes.c_double)]),
+        "dg_segment_derive_column": (ctypes.c_int, [vp, cp, P(dg_expr), P(i32), i64, P(dg_derived_info)]),
+        "dg_segment_drop_derived": (ctypes.c_int, [vp, cp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(l, name)
@@ -404,6 +437,9 @@ class FilterProgram:
             self.nodes.append(node)
             self._emit(f.field)
             return
+        if isinstance(f, Q.ExpressionDimFilter):
+            # (the timeseries / topN / groupBy runners rewrite it to a bound on a derived column first)
+            raise UnsupportedQuery(2, "expression filter on this query type")
         dim = _b(f.dimension)
         self._keep.append(dim)
         node.dimension = dim
@@ -484,6 +520,13 @@ def make_scan(query, query_module, cancel: Optional[ctypes.c_int32] = None, segm
     segments: the segments of the call (predicate filters are resolved over their dictionaries);
     filters=False leaves the query and aggregator filters out (merges only need the aggregators)."""
     keep = []
+    if filters and query_module.query_uses_expressions(query):
+        # an aggregator expression, a virtual column or an expression filter: the runners lower them to derived
+        # columns before they build a call; a query that still carries one here is lowered now (never read as 0)
+        if not segments:
+            raise UnsupportedQuery(2, "expressions need the call's segments")
+        from . import virtual
+        query = virtual.lower_query(query, segments, cancel=cancel)
     fp = FilterProgram(query.effective_filter() if filters else None, query_module, segments)
     keep.append(fp)
     # (a first/last aggregator is followed by its DG_AGG_PAIR_TIME entry: no field, no filter of its own)

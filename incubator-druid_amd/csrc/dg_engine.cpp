@@ -7181,6 +7181,200 @@ extern "C" int dg_segment_numeric_dim_values(dg_segment* s, const char* column, 
   return DG_OK;
 }
 
+// ---- derived columns (include/druidgpu.h: dg_segment_derive_column) ----
+static_assert(sizeof(dg_expr_op) == sizeof(ExOp) && offsetof(dg_expr_op, arg) == offsetof(ExOp, arg) &&
+                  offsetof(dg_expr_op, imm) == offsetof(ExOp, imm),
+              "dg_expr_op is the evaluator's ExOp");
+static_assert(DG_COL_LONG == EX_COL_LONG && DG_COL_FLOAT == EX_COL_FLOAT && DG_COL_DOUBLE == EX_COL_DOUBLE,
+              "the evaluator's column types are the ABI's");
+static_assert(DG_EXPR_MAX_OPS == kExprMaxOps && DG_EXPR_MAX_STACK == kExprMaxStack && DG_EXPR_MAX_INPUTS == kExprMaxInputs &&
+                  DG_EXPR_IDIV == EX_IDIV && DG_EXPR_SELECT == EX_SELECT && DG_EXPR_D2F == EX_D2F,
+              "the evaluator's caps and ops are the ABI's");
+
+static const char* expr_check_text(int code) {
+  switch (code) {
+    case -1: return "program length";
+    case -2: return "unknown op";
+    case -3: return "input index or type";
+    case -4: return "stack underflow";
+    case -5: return "more than DG_EXPR_MAX_STACK operands alive";
+    case -6: return "operand types differ or do not fit the op";
+    case -7: return "does not end with exactly one value";
+    case -8: return "the result's type is not the output type";
+    case -9: return "DG_EXPR_D2F is not the last op of a FLOAT output";
+    case -10: return "input count";
+    default: return "output type";
+  }
+}
+
+// The build: the inputs' views through the ordinary decode path (any codec / long encoding / a segment from
+// rows), one k_expr_eval launch into a flat CODEC_NONE column sized like dg_segment_from_rows' (its tail
+// zeroed: the four-row wide loads of dg_device.h read past the last row), the poisoned-row count read back
+// at the one wait. The segment takes the column only after a build that ran to its end and poisoned nothing.
+extern "C" int dg_segment_derive_column(dg_segment* s, const char* name, const dg_expr* e, const volatile int32_t* cancel,
+                                        int64_t timeout_ms, dg_derived_info* out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  Segment* seg = reinterpret_cast<Segment*>(s);
+  if (!seg || !name || !*name || !e) return set_error(DG_ERR_ARG, "null argument");
+  if (out) memset(out, 0, sizeof *out);
+  if (e->n_ops < 1 || e->n_ops > DG_EXPR_MAX_OPS || !e->ops)
+    return set_error(DG_ERR_ARG, "expression of %d ops (1..%d)", e->n_ops, DG_EXPR_MAX_OPS);
+  if (e->n_inputs < 0 || e->n_inputs > DG_EXPR_MAX_INPUTS || (e->n_inputs > 0 && !e->inputs))
+    return set_error(DG_ERR_ARG, "expression over %d inputs (0..%d)", e->n_inputs, DG_EXPR_MAX_INPUTS);
+  if (e->out_type != DG_COL_LONG && e->out_type != DG_COL_DOUBLE && e->out_type != DG_COL_FLOAT)
+    return set_error(DG_ERR_ARG, "derived column type %d", e->out_type);
+  Context* ctx = seg->ctx;
+  CallGuard g(ctx);
+  CallScratch* cs = g.cs;
+  hipStream_t st = ctx->stream;
+  const ExOp* ops = reinterpret_cast<const ExOp*>(e->ops);
+  std::vector<std::string> in_names;
+  std::vector<const Column*> in_cols;
+  int32_t in_type[kExprMaxInputs] = {};
+  for (int k = 0; k < e->n_inputs; ++k) {
+    if (!e->inputs[k]) return set_error(DG_ERR_ARG, "expression input %d is null", k);
+    const Column* c = seg->find(e->inputs[k]);
+    if (!c) return set_error(DG_ERR_UNSUPPORTED, "expression input %s: the segment has no such column", e->inputs[k]);
+    if (c->derived) return set_error(DG_ERR_ARG, "expression input %s is a derived column", e->inputs[k]);
+    if (c->multi_value || !is_numeric_type(c->type))
+      return set_error(DG_ERR_UNSUPPORTED, "expression input %s is not a numeric column", e->inputs[k]);
+    if (c->data.total != seg->nrows)
+      return set_error(DG_ERR_FORMAT, "column %s holds %d rows, its segment %lld", c->name.c_str(), c->data.total, (long long)seg->nrows);
+    in_names.push_back(e->inputs[k]);
+    in_cols.push_back(c);
+    in_type[k] = c->type;
+  }
+  ExprProg prog;
+  const int chk = ex_check(ops, e->n_ops, in_type, e->n_inputs, e->out_type, &prog);
+  if (chk) return set_error(DG_ERR_ARG, "expression rejected: %s", expr_check_text(chk));
+  if (const Column* old = seg->find(name)) {
+    if (!old->derived) return set_error(DG_ERR_ARG, "%s is a stored column", name);
+    const bool same = old->type == e->out_type && old->ex_inputs == in_names && (int)old->ex_ops.size() == e->n_ops &&
+                      std::equal(old->ex_ops.begin(), old->ex_ops.end(), ops, [](const ExOp& a, const ExOp& b) {
+                        return a.op == b.op && a.arg == b.arg && a.imm == b.imm;
+                      });
+    if (!same) return set_error(DG_ERR_ARG, "%s is a derived column of another expression", name);
+    if (out) {
+      out->type = old->type;
+      out->rows = seg->nrows;
+      out->device_bytes = (int64_t)(old->data.raw.n + old->data.block_ptrs.n);
+    }
+    return DG_OK;
+  }
+  dg_scan timing;
+  memset(&timing, 0, sizeof timing);
+  timing.cancel = cancel;
+  timing.timeout_ms = timeout_ms;
+  Interrupt intr(&timing, t0);
+  cs->intr = &intr;
+  DG_CHECK_INTERRUPT(intr);
+  const int64_t nrows = seg->nrows;
+  std::unique_ptr<Column> col(new Column());
+  col->name = name;
+  col->type = e->out_type;
+  col->derived = true;
+  col->ex_ops.assign(ops, ops + e->n_ops);
+  col->ex_inputs = in_names;
+  BlockColumn& b = col->data;
+  b.total = (int32_t)nrows;
+  b.width = e->out_type == DG_COL_FLOAT ? 4 : 8;
+  b.codec = CODEC_NONE;
+  const size_t bytes = (size_t)nrows * b.width;
+  constexpr size_t kTail = 64;
+  while ((2 << b.log2_per) <= kBlockBytes / b.width) b.log2_per++;
+  b.size_per = 1 << b.log2_per;
+  b.nblocks = (int32_t)((nrows + b.size_per - 1) / b.size_per);
+  b.stored_bytes = (int64_t)bytes;
+  std::vector<const uint8_t*> ptrs(b.nblocks > 0 ? b.nblocks : 1);
+  if (!b.raw.alloc(bytes + kTail) || !b.block_ptrs.alloc(ptrs.size() * sizeof(void*)))
+    return set_error(DG_ERR_OOM, "derived column %s of %zu bytes", name, bytes);
+  for (int32_t k = 0; k < b.nblocks; ++k) ptrs[k] = b.raw.as<uint8_t>() + (size_t)k * (size_t)b.size_per * (size_t)b.width;
+  DG_HIP(hipMemcpy(b.block_ptrs.p, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice));
+  float build_ms = 0;
+  unsigned long long* h_poison = nullptr;
+  auto body = [&]() -> int {
+    DG_HIP(hipEventRecord(ctx->ev[6], st));
+    DG_HIP(hipMemsetAsync(b.raw.as<uint8_t>() + bytes, 0, kTail, st));
+    DecodeBatch db;
+    ExprInputs in;
+    memset(&in, 0, sizeof in);
+    for (int k = 0; k < e->n_inputs; ++k) {
+      const int rc = column_view(in_cols[k], cs, &db, &in.v[k], st);
+      if (rc) return rc;
+    }
+    unsigned long long* d_poison;
+    unsigned long long* s_poison = up_take<unsigned long long>(cs, 1, &d_poison, st);
+    h_poison = host_take<unsigned long long>(cs, 1);
+    if (!s_poison || !h_poison) return set_error(DG_ERR_OOM, "derived column scratch");
+    *s_poison = 0;
+    *h_poison = 0;
+    int rc = run_decodes(cs, &db, st);
+    if (rc) return rc;
+    DG_FLUSH(cs, st);
+    DG_CHECK_INTERRUPT(intr);
+    launch_expr_eval(prog, in, nrows, b.raw.p, d_poison, st);
+    DG_HIP(hipEventRecord(ctx->ev[7], st));
+    cs->late.push_back({h_poison, d_poison, 8});
+    rc = finish_call(cs, st);
+    if (rc) return rc;
+    DG_HIP(hipEventElapsedTime(&build_ms, ctx->ev[6], ctx->ev[7]));
+    return DG_OK;
+  };
+  const int rc = body();
+  if (rc) {  // (queued kernels still use the buffers freed on return)
+    hipStreamSynchronize(st);
+    return rc;
+  }
+  if (out) {
+    out->type = e->out_type;
+    out->rows = nrows;
+    out->poisoned_rows = (int64_t)*h_poison;
+    out->build_ms = build_ms;
+  }
+  if (*h_poison)
+    return set_error(DG_ERR_UNSUPPORTED, "expression: division by zero in %llu rows", *h_poison);
+  const int64_t dev_bytes = (int64_t)(b.raw.n + b.block_ptrs.n);
+  if (out) {
+    out->built = 1;
+    out->device_bytes = dev_bytes;
+  }
+  seg->device_bytes += dev_bytes;
+  seg->by_name[col->name] = col.get();
+  seg->derived.push_back(std::move(col));
+  return DG_OK;
+}
+
+extern "C" int dg_segment_drop_derived(dg_segment* s, const char* name) {
+  Segment* seg = reinterpret_cast<Segment*>(s);
+  if (!seg || !name) return set_error(DG_ERR_ARG, "null argument");
+  Context* ctx = seg->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  hipSetDevice(ctx->device);
+  Column* c = seg->find(name);
+  if (!c) return set_error(DG_ERR_NOT_FOUND, "no column %s", name);
+  if (!c->derived) return set_error(DG_ERR_ARG, "%s is a stored column", name);
+  // (no call runs: the context's mutex is held; a failed call drained its streams before it returned)
+  int64_t bytes = (int64_t)(c->data.raw.n + c->data.block_ptrs.n);
+  if (c->nd_ready) bytes += (int64_t)(c->nd_ids.n + c->nd_vals.n);
+  if (c->vcnt_ready) bytes += (int64_t)c->vcnt.n;
+  if (c->tix_ready) bytes += (int64_t)(c->tix_perm.n + c->tix_lid.n + c->tix_base.n);
+  seg->device_bytes -= bytes;
+  // merged dictionaries of calls that grouped by the column: another expression may take the name
+  auto& dc = ctx->dict_cache;
+  dc.erase(std::remove_if(dc.begin(), dc.end(),
+                          [&](const std::shared_ptr<MergedDict>& d) {
+                            return d->dim == name && std::find(d->uids.begin(), d->uids.end(), seg->uid) != d->uids.end();
+                          }),
+           dc.end());
+  seg->by_name.erase(name);
+  for (auto it = seg->derived.begin(); it != seg->derived.end(); ++it)
+    if (it->get() == c) {
+      seg->derived.erase(it);
+      break;
+    }
+  return DG_OK;
+}
+
 extern "C" int dg_debug_lz4_classify(const uint8_t* block, int32_t len, int32_t* kind) {
   if (!block || len <= 0 || len > kBlockBytes + 2048 || !kind) return set_error(DG_ERR_ARG, "bad arguments");
   std::vector<uint32_t> one;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/druidgpu.h"
+#include "dg_expr.h"
 #include "dg_filter_plan.h"
 #include "dg_postagg.h"
 
@@ -463,6 +464,12 @@ struct Column : DictColumn {
   int64_t nd_card = 0;
   double nd_build_ms = 0;
   bool nd_ready = false;
+  // a derived column (dg_segment_derive_column): `data` is a flat CODEC_NONE column the expression kernel wrote
+  // (dg_expr.hip), registered under a name the caller chose and kept until dropped or until the segment is
+  // released; the program it was built from tells an identical request from a colliding one
+  bool derived = false;
+  std::vector<ExOp> ex_ops;
+  std::vector<std::string> ex_inputs;
 };
 constexpr int kNdLog2Per = 31;  // rows of a segment are int32: every row lies in block 0
 
@@ -577,6 +584,8 @@ struct Segment {
   int64_t min_time = 0, max_time = 0;
   int bitmap_roaring = 0;
   std::vector<std::unique_ptr<Column>> columns;
+  // derived columns (dg_segment_derive_column): found by name like the stored ones, not listed among them
+  std::vector<std::unique_ptr<Column>> derived;
   std::map<std::string, Column*> by_name;
   // the dimension list (index.drd's `dims`, StorageAdapter.getAvailableDimensions; a segment from rows:
   // its string columns in the order given): the scan query's default column list puts them first
@@ -741,6 +750,15 @@ void launch_nd_unique_emit(const uint64_t* words, int64_t n, const uint32_t* til
                            int64_t card, hipStream_t s);
 // ids[r] = lower bound of v[r] in vals[0 .. card)
 void launch_nd_encode(const ColView& v, int64_t nrows, const int64_t* vals, uint32_t card, uint32_t* ids, hipStream_t s);
+// ---- derived columns (dg_expr.hip; Column::derived) ----
+// the decoded views of a program's input columns (EX_INPUT arg indexes them)
+struct ExprInputs {
+  ColView v[kExprMaxInputs];
+};
+// out[r] = the checked program over row r for r < nrows (8-byte words; a FLOAT output: 4-byte float32); a row
+// whose value depends on a long division by zero stores 0 and adds one to *poisoned (zeroed by the caller)
+void launch_expr_eval(const ExprProg& p, const ExprInputs& in, int64_t nrows, void* out, unsigned long long* poisoned,
+                      hipStream_t s);
 // ---- first / last aggregators (dg_firstlast.hip) ----
 // One segment's key column: keys[r] = ((((t(r) - t0) << rb) | p(r)) + 1) ^ sign, p(r) = p0 + r (ascending
 // cursor; groupBy: p0 = the segment's row_base) or p0 - r (descending: p0 = nrows - 1).

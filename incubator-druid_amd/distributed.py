@@ -102,6 +102,15 @@ def _refuse_pairs(query, what: str):
             raise R.N.UnsupportedQuery(2, f"{a.type}({a.name}): {what} does not combine first/last pairs")
 
 
+def _refuse_virtual_dimensions(query, dims, what: str):
+    """A dimension over a virtual column is a derived LONG column per segment (virtual.lower_query): like every
+    numeric dimension it has no cluster-wide dictionary here."""
+    virtual = {v.name for v in getattr(query, "virtualColumns", [])} | set(getattr(query, "derivedDimensions", {}))
+    for d in dims:
+        if d in virtual:
+            raise R.N.UnsupportedQuery(2, f"{what} over the virtual column {d}")
+
+
 def _refuse_post_aggregations(query, what: str):
     """The cross-process merges exchange aggregator slots only: a query with post-aggregators (whose topN
     ranking and groupBy having / ORDER BY may depend on them) is refused before any collective."""
@@ -214,6 +223,7 @@ def gather_topn(dist, query: Q.TopNQuery, raw: "R.TopNRaw", gdict: GlobalDiction
     dictionary here."""
     _refuse_pairs(query, "the cross-process topN gather")
     _refuse_post_aggregations(query, "the cross-process topN gather")
+    _refuse_virtual_dimensions(query, [query.dimension], "the cross-process topN gather")
     if query.dimension_type != "STRING" or any(s.column_type(query.dimension) in R._NUMERIC_COLS
                                                for s in (segments or getattr(raw, "segments", None) or [])):
         raise R.N.UnsupportedQuery(2, f"topN on numeric dimension {query.dimension} across processes")
@@ -372,6 +382,7 @@ class GroupByExchange:
     def __init__(self, dist, query: Q.GroupByQuery, segments, engine=None):
         _refuse_pairs(query, "the cross-process groupBy merge")
         _refuse_post_aggregations(query, "the cross-process groupBy merge")
+        _refuse_virtual_dimensions(query, query.dimensions, "the cross-process groupBy merge")
         self.dist, self.query = dist, query
         self.world, self.rank = dist.get_world_size(), dist.get_rank()
         self.engine = engine if engine is not None else NativeMerge(segments[0].context)

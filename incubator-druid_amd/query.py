@@ -13,6 +13,11 @@ fed in unchanged (``Query.from_json``):
   query/groupby/GroupByQuery.java, query/search/SearchQuery.java; topN metric specs
   NumericTopNMetricSpec / InvertedTopNMetricSpec / DimensionTopNMetricSpec.
 
+* numeric expressions: common/.../math/expr (Expr.g4, Expr, Function, ExprEval, Evals) as a parser, a
+  per-segment type checker and a compiler to the postfix programs of dg_segment_derive_column;
+  ExpressionVirtualColumn, the aggregators' ``expression`` and ExpressionDimFilter (virtual.py lowers them
+  to derived columns before a query runs)
+
 Only the null-handling mode the reference defaults to is modelled
 (``druid.generic.useDefaultValueForNull=true``, common/config/NullHandling.java:34,54):
 null string == "" and numeric nulls read as 0.
@@ -284,6 +289,8 @@ class DimFilter:
             return SearchQueryDimFilter(js["dimension"], dict(js["query"]))
         if t == "like":
             return LikeDimFilter(js["dimension"], js["pattern"], js.get("escape"))
+        if t == "expression":
+            return ExpressionDimFilter(js["expression"])
         raise ValueError(f"unsupported filter type {t!r}")
 
 
@@ -497,6 +504,20 @@ class LikeDimFilter(DimFilter):
 PREDICATE_FILTERS = (RegexDimFilter, SearchQueryDimFilter, LikeDimFilter)
 
 
+@dataclass
+class ExpressionDimFilter(DimFilter):
+    """query/filter/ExpressionDimFilter.java -> segment/filter/ExpressionFilter.java:54-66: a row matches when
+    Evals.asBoolean(selector.getLong()) holds, i.e. the expression's value cast to a long is above 0 (0.5 does
+    not match). The runners evaluate it into a derived LONG column and filter that with a numeric bound."""
+    expression: str
+
+    def __post_init__(self):
+        self.ast = parse_expression(self.expression)
+
+    def to_json(self):
+        return {"type": "expression", "expression": self.expression}
+
+
 # ----------------------------------------------------------------------------------------------
 # aggregators
 # ----------------------------------------------------------------------------------------------
@@ -572,10 +593,22 @@ class AggregatorFactory:
     name: str
     fieldName: Optional[str] = None
     filter: Optional["DimFilter"] = None
+    # SimpleLong / SimpleDouble / SimpleFloatAggregatorFactory: the input is an expression instead of a column
+    # (sum, min and max factories; the first/last factories have no such field in the reference)
+    expression: Optional[str] = None
 
     def __post_init__(self):
         if self.type not in AGG_KINDS:
             raise ValueError(f"unsupported aggregator type {self.type!r}")
+        if self.expression is not None:
+            if self.kind == 0 or self.is_pair:
+                raise ValueError(f"aggregator type {self.type!r} has no expression field")
+            if self.fieldName is not None:
+                # SimpleDoubleAggregatorFactory.java:59
+                raise ValueError("Must have a valid, non-null fieldName or expression: exactly one of them")
+            self.ast = parse_expression(self.expression)
+        elif self.kind != 0 and self.fieldName is None:
+            raise ValueError("Must have a valid, non-null fieldName or expression")
 
     @property
     def kind(self) -> int:
@@ -655,6 +688,8 @@ class AggregatorFactory:
         js = {"type": self.type, "name": self.name}
         if self.fieldName is not None:
             js["fieldName"] = self.fieldName
+        if self.expression is not None:
+            js["expression"] = self.expression
         if self.filter is not None:
             return {"type": "filtered", "filter": self.filter.to_json(), "aggregator": js}
         return js
@@ -670,8 +705,8 @@ class AggregatorFactory:
                 raise ValueError("filtered aggregator without a filter")
             # FilteredAggregatorFactory(FilteredAggregatorFactory(x, f1), f2) matches f2 and then f1
             both = f if inner.filter is None else AndDimFilter([f, inner.filter])
-            return AggregatorFactory(inner.type, inner.name, inner.fieldName, both)
-        return AggregatorFactory(js["type"], js["name"], js.get("fieldName"))
+            return AggregatorFactory(inner.type, inner.name, inner.fieldName, both, inner.expression)
+        return AggregatorFactory(js["type"], js["name"], js.get("fieldName"), None, js.get("expression"))
 
 
 def filtered(agg: AggregatorFactory, flt) -> AggregatorFactory:
@@ -704,6 +739,7 @@ class _PairTime(AggregatorFactory):
 
     def __init__(self, pair: AggregatorFactory):
         self.type, self.name, self.fieldName, self.filter = "pairTime", pair.name + "\x00time", None, None
+        self.expression = None
 
     @property
     def kind(self) -> int:
@@ -1269,6 +1305,615 @@ class TopNMetricSpec:
 
 
 # ----------------------------------------------------------------------------------------------
+# numeric expressions (common/.../math/expr: Expr.g4, ExprListenerImpl, Expr, Function, ExprEval, Evals)
+# ----------------------------------------------------------------------------------------------
+def UnsupportedExpression(msg: str):
+    """UnsupportedQuery for an expression construct the engine has no program for: the caller keeps its CPU
+    engine."""
+    from ._native import UnsupportedQuery
+    return UnsupportedQuery(2, msg)
+
+
+# ops of a compiled expression (DG_EXPR_* of include/druidgpu.h)
+(EX_INPUT, EX_CONST_L, EX_CONST_D, EX_L2D, EX_D2L, EX_D2F, EX_ADD, EX_SUB, EX_MUL, EX_DIV, EX_MOD, EX_NEG, EX_NOT,
+ EX_LT, EX_LE, EX_GT, EX_GE, EX_EQ, EX_NE, EX_AND, EX_OR, EX_SELECT, EX_ABS, EX_CEIL, EX_FLOOR, EX_MIN, EX_MAX,
+ EX_IDIV) = range(28)
+EXPR_MAX_OPS, EXPR_MAX_STACK, EXPR_MAX_INPUTS = 64, 16, 8
+_EX_BINARY = {"+": EX_ADD, "-": EX_SUB, "*": EX_MUL, "/": EX_DIV, "%": EX_MOD, "<": EX_LT, "<=": EX_LE, ">": EX_GT,
+              ">=": EX_GE, "==": EX_EQ, "!=": EX_NE, "&&": EX_AND, "||": EX_OR}
+# every function the reference knows (Function.java; the macro table's: ExprMacroTable + query/expression/*):
+# a name outside this list is a syntax error there, one inside it that the engine lacks is refused
+# (names as Parser.FUNCTIONS keys them: lower-cased)
+_EX_TRANSCENDENTAL = ("acos", "asin", "atan", "cbrt", "cos", "cosh", "exp", "expm1", "getexponent", "log", "log10",
+                      "log1p", "nextup", "rint", "round", "signum", "sin", "sinh", "sqrt", "tan", "tanh", "todegrees",
+                      "toradians", "ulp", "atan2", "copysign", "hypot", "remainder", "nextafter", "pow", "scalb")
+_EX_STRING_FNS = ("concat", "strlen", "strpos", "substring", "replace", "lower", "upper", "like", "regexp_extract",
+                  "lookup", "trim", "ltrim", "rtrim")
+_EX_TIME_FNS = ("timestamp", "unix_timestamp", "timestamp_ceil", "timestamp_floor", "timestamp_shift",
+                "timestamp_extract", "timestamp_format", "timestamp_parse")
+_EX_NULL_FNS = ("nvl", "isnull", "notnull", "case_simple")
+_EX_SUPPORTED_FNS = {"abs": 1, "ceil": 1, "floor": 1, "min": 2, "max": 2, "div": 2, "if": 3, "cast": 2,
+                     "case_searched": None}
+
+_EX_TOKEN = re.compile(r"""
+    (?P<ws>[ \t\r\n]+)
+  | (?P<double>[0-9]+\.[0-9]*)
+  | (?P<long>[0-9]+)
+  | (?P<id>[_$a-zA-Z][_$a-zA-Z0-9]*)
+  | (?P<qid>"(?:\\(?:['"\\/bfnrt]|u[0-9a-fA-F]{4})|[^"\\])*")
+  | (?P<str>'(?:\\(?:['"\\/bfnrt]|u[0-9a-fA-F]{4})|[^'\\])*')
+  | (?P<op><=|>=|==|!=|&&|\|\||[-!^*/%+<>(),])
+""", re.X)
+_EX_ESCAPES = {"b": "\b", "f": "\f", "n": "\n", "r": "\r", "t": "\t", "'": "'", '"': '"', "\\": "\\", "/": "/"}
+
+
+def _unescape_java(s: str) -> str:
+    """StringEscapeUtils.unescapeJava over the escapes the lexer admits."""
+    out, i = [], 0
+    while i < len(s):
+        c = s[i]
+        if c != "\\":
+            out.append(c)
+            i += 1
+        elif s[i + 1] == "u":
+            out.append(chr(int(s[i + 2:i + 6], 16)))
+            i += 6
+        else:
+            out.append(_EX_ESCAPES[s[i + 1]])
+            i += 2
+    return "".join(out)
+
+
+def _ex_tokens(text: str) -> List[Tuple[str, Any]]:
+    out, pos = [], 0
+    while pos < len(text):
+        m = _EX_TOKEN.match(text, pos)
+        if m is None:
+            raise ValueError(f"expression {text!r}: unexpected character at {pos}")
+        pos = m.end()
+        kind = m.lastgroup
+        if kind == "ws":
+            continue
+        v = m.group()
+        if kind == "long":  # Long.parseLong (ExprListenerImpl.exitLongExpr): the literal has no sign of its own
+            if int(v) > LONG_MAX:
+                raise ValueError(f"expression {text!r}: long literal {v} overflows (NumberFormatException)")
+            out.append(("long", int(v)))
+        elif kind == "double":  # Double.parseDouble: a literal past the range is Infinity
+            try:
+                out.append(("double", float(v)))
+            except OverflowError:
+                out.append(("double", math.inf))
+        elif kind == "id":
+            out.append(("null", None) if v == "null" else ("id", v))
+        elif kind == "qid":
+            out.append(("id", _unescape_java(v[1:-1])))
+        elif kind == "str":
+            out.append(("str", _unescape_java(v[1:-1])))
+        else:
+            out.append(("op", v))
+    return out
+
+
+# binary operators by binding strength, loosest first (Expr.g4: an alternative listed earlier binds tighter;
+# every level is left-associative but '^')
+_EX_LEVELS = [("&&", "||"), ("<", "<=", ">", ">=", "==", "!="), ("+", "-"), ("*", "/", "%"), ("^",)]
+
+
+class _ExParser:
+    def __init__(self, text: str):
+        self.text, self.toks, self.i = text, _ex_tokens(text), 0
+
+    def peek(self):
+        return self.toks[self.i] if self.i < len(self.toks) else ("end", None)
+
+    def take(self):
+        t = self.peek()
+        self.i += 1
+        return t
+
+    def fail(self, what):
+        raise ValueError(f"expression {self.text!r}: {what}")
+
+    def parse(self):
+        e = self.binary(0)
+        if self.peek()[0] != "end":
+            self.fail(f"unexpected {self.peek()[1]!r}")
+        return e
+
+    def binary(self, level):
+        if level == len(_EX_LEVELS):
+            return self.unary()
+        ops = _EX_LEVELS[level]
+        left = self.binary(level + 1)
+        while self.peek() in [("op", o) for o in ops]:
+            op = self.take()[1]
+            if op == "^":  # right-associative
+                return ("bin", op, left, self.binary(level))
+            left = ("bin", op, left, self.binary(level + 1))
+        return left
+
+    def unary(self):
+        t = self.peek()
+        if t in (("op", "-"), ("op", "!")):  # binds tighter than every binary operator: -a ^ b is (-a) ^ b
+            self.take()
+            return ("un", t[1], self.unary())
+        return self.atom()
+
+    def atom(self):
+        kind, v = self.take()
+        if kind in ("long", "double", "str"):
+            return (kind, v)
+        if kind == "null":
+            return ("null",)
+        if kind == "op" and v == "(":
+            e = self.binary(0)
+            if self.take() != ("op", ")"):
+                self.fail("missing ')'")
+            return e
+        if kind == "id":
+            if self.peek() != ("op", "("):
+                return ("id", v)
+            self.take()
+            args = []
+            if self.peek() != ("op", ")"):
+                args.append(self.binary(0))
+                while self.peek() == ("op", ","):
+                    self.take()
+                    args.append(self.binary(0))
+            if self.take() != ("op", ")"):
+                self.fail("missing ')' after function arguments")
+            # (Parser.getFunction and ExprMacroTable.get look the name up lower-cased: IF(a, b, c) is if(a, b, c))
+            return ("fn", v.lower(), args)
+        self.fail("unexpected end" if kind == "end" else f"unexpected {v!r}")
+
+
+def parse_expression(text: str, check: bool = True):
+    """Expr.g4 as an AST of tuples: ("long", v) ("double", v) ("str", s) ("null",) ("id", name) ("un", op, e)
+    ("bin", op, l, r) ("fn", name, [args]). Syntax errors and unknown function names are ValueError; constructs the
+    engine refuses whatever the columns' types are raise UnsupportedQuery here (check_expression; check=False:
+    the tree as the grammar reads it, refused constructs included)."""
+    if not isinstance(text, str):
+        raise ValueError("an expression must be a string")
+    ast = _ExParser(text).parse()
+    if check:
+        check_expression(ast)
+    return ast
+
+
+def check_expression(ast) -> None:
+    """The refusals that do not depend on the columns' types, each naming its construct."""
+    kind = ast[0]
+    if kind == "str":
+        raise UnsupportedExpression("expression: string literal (string expressions stay on the CPU)")
+    if kind == "null":
+        raise UnsupportedExpression("expression: null (the reference types it as a string)")
+    if kind == "un":
+        check_expression(ast[2])
+    elif kind == "bin":
+        if ast[1] == "^":
+            raise UnsupportedExpression("expression: operator ^ (the device's pow is not Java's bit for bit)")
+        check_expression(ast[2])
+        check_expression(ast[3])
+    elif kind == "fn":
+        name, args = ast[1], ast[2]
+        if name in _EX_TRANSCENDENTAL:
+            raise UnsupportedExpression(f"expression: function {name} (its device result is not Java's bit for bit)")
+        if name in _EX_STRING_FNS:
+            raise UnsupportedExpression(f"expression: string function {name}")
+        if name in _EX_TIME_FNS:
+            raise UnsupportedExpression(f"expression: time function {name}")
+        if name in _EX_NULL_FNS:
+            raise UnsupportedExpression(f"expression: function {name} (null handling stays on the CPU)")
+        if name not in _EX_SUPPORTED_FNS:
+            raise ValueError(f"expression: unknown function {name!r}")
+        want = _EX_SUPPORTED_FNS[name]
+        if want is not None and len(args) != want:
+            raise ValueError(f"expression: function {name} needs {want} argument{'s' if want > 1 else ''}")
+        if name == "case_searched":
+            if len(args) < 2:
+                raise ValueError("expression: function case_searched must have at least 2 arguments")
+            if len(args) % 2 == 0:
+                raise UnsupportedExpression("expression: case_searched without an ELSE branch (its value may be null)")
+        if name == "cast":
+            if args[1][0] != "str":
+                raise UnsupportedExpression("expression: cast to a type that is not a literal")
+            t = args[1][1].upper()
+            if t == "STRING":
+                raise UnsupportedExpression("expression: cast to STRING")
+            if t not in ("LONG", "DOUBLE"):
+                raise ValueError(f"expression: invalid type {args[1][1]!r}")
+            check_expression(args[0])
+        else:
+            for a in args:
+                check_expression(a)
+
+
+def expression_identifiers(ast) -> List[str]:
+    """The identifiers of an expression in first-use order (Parser.findRequiredBindings)."""
+    out: List[str] = []
+
+    def walk(n):
+        if n[0] == "id":
+            if n[1] not in out:
+                out.append(n[1])
+        elif n[0] == "un":
+            walk(n[2])
+        elif n[0] == "bin":
+            walk(n[2])
+            walk(n[3])
+        elif n[0] == "fn":
+            for a in n[2]:
+                if a[0] != "str":
+                    walk(a)
+    walk(ast)
+    return out
+
+
+@dataclass
+class ExprProgram:
+    """A compiled expression: ops [(op, arg, imm)] over `inputs` (column names), the stack type its value has
+    ("long" / "double") and, once with_output gave it one, the derived column's type."""
+    ops: List[Tuple[int, int, int]]
+    inputs: List[str]
+    type: str
+    out_type: Optional[str] = None
+
+    def with_output(self, out_type: str) -> "ExprProgram":
+        """The program whose value is cast to a LONG, DOUBLE or FLOAT column (ExprEval.asLong / asDouble,
+        ExpressionColumnValueSelector.getFloat)."""
+        ops = list(self.ops)
+        if out_type == "LONG":
+            if self.type == "double":
+                ops.append((EX_D2L, 0, 0))
+        elif out_type in ("DOUBLE", "FLOAT"):
+            if self.type == "long":
+                ops.append((EX_L2D, 0, 0))
+            if out_type == "FLOAT":
+                ops.append((EX_D2F, 0, 0))
+        else:
+            raise UnsupportedExpression(f"expression: output type {out_type}")
+        if len(ops) > EXPR_MAX_OPS:
+            raise UnsupportedExpression(f"expression: more than {EXPR_MAX_OPS} ops")
+        return ExprProgram(ops, list(self.inputs), self.type, out_type)
+
+    def natural(self) -> "ExprProgram":
+        return self.with_output("LONG" if self.type == "long" else "DOUBLE")
+
+    def digest(self) -> str:
+        """The derived column's name: a digest of (ops, inputs, output type) behind a prefix no Druid column has
+        (a control character), so equal expressions share a column and different ones cannot collide."""
+        import hashlib
+        h = hashlib.sha1(repr((self.ops, self.inputs, self.out_type)).encode()).hexdigest()
+        return "\x01expr:" + h[:32]
+
+
+def compile_expression(ast, column_type) -> ExprProgram:
+    """Type-check an expression against one segment's columns and compile it to postfix ops.
+    column_type(name) -> "LONG" / "FLOAT" / "DOUBLE", "STRING" or None (no such column); "__time" is LONG."""
+    ops: List[Tuple[int, int, int]] = []
+    inputs: List[str] = []
+    types: Dict[int, str] = {}
+    state = {"sp": 0, "max": 0}
+
+    def typeof(n) -> str:
+        t = types.get(id(n))
+        if t is None:
+            t = types[id(n)] = _typeof(n)
+        return t
+
+    def _typeof(n) -> str:
+        k = n[0]
+        if k in ("long", "double"):
+            return k
+        if k == "id":
+            ct = "LONG" if n[1] == "__time" else column_type(n[1])
+            if ct is None:
+                raise UnsupportedExpression(f"expression: the segment has no column {n[1]} (it would read null)")
+            if ct not in ("LONG", "FLOAT", "DOUBLE"):
+                raise UnsupportedExpression(f"expression: column {n[1]} is not numeric")
+            return "long" if ct == "LONG" else "double"
+        if k == "un":
+            return typeof(n[2])
+        if k == "bin":
+            lt, rt = typeof(n[2]), typeof(n[3])
+            if n[1] in ("&&", "||"):
+                if lt != rt:
+                    raise UnsupportedExpression(f"expression: operands of {n[1]} differ in type "
+                                                "(the value's type would differ from row to row)")
+                return lt
+            return "long" if lt == rt == "long" else "double"
+        name, args = n[1], n[2]
+        if name in ("ceil", "floor"):
+            typeof(args[0])
+            return "double"
+        if name == "abs":
+            return typeof(args[0])
+        if name in ("min", "max"):
+            return "long" if typeof(args[0]) == typeof(args[1]) == "long" else "double"
+        if name == "div":
+            typeof(args[0]), typeof(args[1])
+            return "long"
+        if name == "cast":
+            typeof(args[0])
+            return args[1][1].lower()
+        branches = [args[1], args[2]] if name == "if" else [args[i] for i in range(1, len(args), 2)] + [args[-1]]
+        conds = [args[0]] if name == "if" else [args[i] for i in range(0, len(args) - 1, 2)]
+        for c in conds:
+            typeof(c)
+        ts = {typeof(b) for b in branches}
+        if len(ts) != 1:
+            raise UnsupportedExpression(f"expression: branches of {'if' if name == 'if' else 'case'} differ in type "
+                                        "(the value's type would differ from row to row)")
+        return ts.pop()
+
+    def push(op, arg=0, imm=0, pops=0):
+        ops.append((op, arg, imm & ((1 << 64) - 1)))
+        state["sp"] += 1 - pops
+        state["max"] = max(state["max"], state["sp"])
+
+    def emit_as(n, want: str):
+        emit(n)
+        if typeof(n) != want:
+            push(EX_L2D if want == "double" else EX_D2L, pops=1)
+
+    def constant(n):
+        """The value of a subexpression without identifiers, or None."""
+        if expression_identifiers(n):
+            return None
+        sub = compile_expression(n, lambda name: None)
+        return run_expression(sub.ops, [])
+
+    def emit(n):
+        k = n[0]
+        if k == "long":
+            push(EX_CONST_L, imm=n[1])
+        elif k == "double":
+            push(EX_CONST_D, imm=double_bits(n[1]))
+        elif k == "id":
+            typeof(n)
+            if n[1] not in inputs:
+                inputs.append(n[1])
+            push(EX_INPUT, arg=inputs.index(n[1]))
+        elif k == "un":
+            emit(n[2])
+            push(EX_NEG if n[1] == "-" else EX_NOT, pops=1)
+        elif k == "bin":
+            op, t = n[1], typeof(n)
+            operand = t if op in ("&&", "||") else ("long" if typeof(n[2]) == typeof(n[3]) == "long" else "double")
+            if op in ("/", "%") and operand == "long":
+                zero_divisor(n[2], n[3])
+            emit_as(n[2], operand)
+            emit_as(n[3], operand)
+            push(_EX_BINARY[op], pops=2)
+        else:
+            name, args = n[1], n[2]
+            if name in ("abs", "ceil", "floor"):
+                emit_as(args[0], "double" if name != "abs" else typeof(args[0]))
+                push({"abs": EX_ABS, "ceil": EX_CEIL, "floor": EX_FLOOR}[name], pops=1)
+            elif name in ("min", "max", "div"):
+                operand = "long" if typeof(args[0]) == typeof(args[1]) == "long" else "double"
+                if name == "div" and operand == "long":
+                    zero_divisor(args[0], args[1])
+                emit_as(args[0], operand)
+                emit_as(args[1], operand)
+                push({"min": EX_MIN, "max": EX_MAX, "div": EX_IDIV}[name], pops=2)
+            elif name == "cast":
+                emit_as(args[0], typeof(n))
+            else:  # if / case_searched: c1 ? a1 : (c2 ? a2 : ... else)
+                typeof(n)
+                rest = list(args)
+
+                def chain(rest):
+                    if len(rest) == 1:
+                        emit(rest[0])
+                        return
+                    emit(rest[0])
+                    emit(rest[1])
+                    chain(rest[2:])
+                    push(EX_SELECT, pops=3)
+                chain(rest)
+
+    def zero_divisor(l, r):
+        # Parser.flatten evaluates a constant subexpression while parsing: a long division by zero throws there
+        if not expression_identifiers(l) and not expression_identifiers(r):
+            c = constant(r)
+            if c is not None and c[0] == 0:
+                raise UnsupportedExpression("expression: a constant subexpression divides a long by zero "
+                                            "(ArithmeticException while parsing)")
+
+    t = typeof(ast)
+    emit(ast)
+    if len(inputs) > EXPR_MAX_INPUTS:
+        raise UnsupportedExpression(f"expression: more than {EXPR_MAX_INPUTS} input columns")
+    if len(ops) > EXPR_MAX_OPS:
+        raise UnsupportedExpression(f"expression: more than {EXPR_MAX_OPS} ops")
+    if state["max"] > EXPR_MAX_STACK:
+        raise UnsupportedExpression(f"expression: more than {EXPR_MAX_STACK} operands alive at once")
+    return ExprProgram(ops, inputs, t)
+
+
+def _java_ldiv(a: int, b: int) -> int:
+    q = abs(a) // abs(b)
+    return _wrap64(q if (a < 0) == (b < 0) else -q)
+
+
+def _java_lmod(a: int, b: int) -> int:
+    return a - b * (abs(a) // abs(b) * (1 if (a < 0) == (b < 0) else -1))
+
+
+def java_fmod(x: float, y: float) -> float:
+    """Java's double % (JLS 15.17.3) = C fmod."""
+    if x != x or y != y or math.isinf(x) or y == 0.0:
+        return math.nan
+    if math.isinf(y):
+        return x
+    return math.fmod(x, y)
+
+
+def _java_ceil_floor(x: float, up: bool) -> float:
+    if x != x or math.isinf(x):
+        return x
+    r = float(math.ceil(x) if up else math.floor(x))
+    return math.copysign(r, x) if r == 0.0 else r
+
+
+def _bits_double(u: int) -> float:
+    return struct.unpack("<d", struct.pack("<Q", u))[0]
+
+
+def run_expression(ops: Sequence[Tuple[int, int, int]], row: Sequence[Tuple[str, Any]]):
+    """The evaluator of csrc/dg_expr.h in Python, for one row: row[k] = ("LONG" | "DOUBLE" | "FLOAT", value) of
+    input k. Returns (word, poisoned): the final 64-bit word (a long as unsigned, a double's canonical bits, a
+    D2F result's float32 bits) and whether it depends on a long division by zero."""
+    M = (1 << 64) - 1
+    st: List[Tuple[str, Any, bool]] = []  # (type, value, poisoned); a long as a signed int, a double as a float
+
+    def truth(e):
+        return e[1] > 0
+
+    for op, arg, imm in ops:
+        if op == EX_INPUT:
+            t, v = row[arg]
+            st.append(("long", _wrap64(int(v)), False) if t == "LONG" else
+                      ("double", _f32(v) if t == "FLOAT" else float(v), False))
+        elif op == EX_CONST_L:
+            st.append(("long", _wrap64(imm), False))
+        elif op == EX_CONST_D:
+            st.append(("double", _bits_double(imm), False))
+        elif op in (EX_L2D, EX_D2L, EX_D2F, EX_NEG, EX_NOT, EX_ABS, EX_CEIL, EX_FLOOR):
+            t, v, p = st.pop()
+            if op == EX_L2D:
+                st.append(("double", float(v), p))
+            elif op == EX_D2L:
+                st.append(("long", java_d2l(v), p))
+            elif op == EX_D2F:
+                f = struct.unpack("<f", struct.pack("<I", 0x7FC00000))[0] if v != v else _f32_round(v)
+                st.append(("float", f, p))
+            elif op == EX_NEG:
+                st.append((t, _wrap64(-v) if t == "long" else -v, p))
+            elif op == EX_NOT:
+                b = not truth((t, v))
+                st.append((t, int(b) if t == "long" else float(b), p))
+            elif op == EX_ABS:
+                st.append((t, _wrap64(abs(v)) if t == "long" else abs(v), p))
+            else:
+                st.append((t, _java_ceil_floor(v, op == EX_CEIL), p))
+        elif op == EX_SELECT:
+            b, a, c = st.pop(), st.pop(), st.pop()
+            pick = a if truth(c) else b
+            st.append((pick[0], pick[1], c[2] or pick[2]))
+        else:
+            b, a = st.pop(), st.pop()
+            t, x, y, p = a[0], a[1], b[1], a[2] or b[2]
+            if op in (EX_AND, EX_OR):
+                right = truth(a) if op == EX_AND else not truth(a)
+                pick = b if right else a
+                st.append((pick[0], pick[1], a[2] or (right and b[2])))
+            elif t == "long":
+                if op in (EX_DIV, EX_IDIV, EX_MOD) and y == 0:
+                    st.append(("long", 0, True))
+                    continue
+                r = {EX_ADD: lambda: x + y, EX_SUB: lambda: x - y, EX_MUL: lambda: x * y,
+                     EX_DIV: lambda: _java_ldiv(x, y), EX_IDIV: lambda: _java_ldiv(x, y),
+                     EX_MOD: lambda: _java_lmod(x, y), EX_LT: lambda: int(x < y), EX_LE: lambda: int(x <= y),
+                     EX_GT: lambda: int(x > y), EX_GE: lambda: int(x >= y), EX_EQ: lambda: int(x == y),
+                     EX_NE: lambda: int(x != y), EX_MIN: lambda: min(x, y), EX_MAX: lambda: max(x, y)}[op]()
+                st.append(("long", _wrap64(r), p))
+            else:
+                cmp = java_double_compare(x, y)
+                if op == EX_IDIV:
+                    st.append(("long", java_d2l(java_double_div(x, y)), p))
+                    continue
+                r = {EX_ADD: lambda: x + y, EX_SUB: lambda: x - y, EX_MUL: lambda: x * y,
+                     EX_DIV: lambda: java_double_div(x, y), EX_MOD: lambda: java_fmod(x, y),
+                     EX_LT: lambda: float(cmp < 0), EX_LE: lambda: float(cmp <= 0), EX_GT: lambda: float(cmp > 0),
+                     EX_GE: lambda: float(cmp >= 0), EX_EQ: lambda: float(x == y), EX_NE: lambda: float(x != y),
+                     EX_MIN: lambda: java_min(x, y) if y == y else y,
+                     EX_MAX: lambda: java_max(x, y) if y == y else y}[op]()
+                st.append(("double", r, p))
+    t, v, p = st.pop()
+    if t == "long":
+        return v & M, p
+    if t == "float":
+        return (0x7FC00000 if v != v else struct.unpack("<I", struct.pack("<f", v))[0]), p
+    return double_bits(v), p
+
+
+def _f32_round(d: float) -> float:
+    """Java's (float) double: round to nearest even, past the range an infinity (struct.pack raises there)."""
+    try:
+        return _f32(d)
+    except OverflowError:
+        return math.copysign(math.inf, d)
+
+
+@dataclass
+class ExpressionVirtualColumn:
+    """segment/virtual/ExpressionVirtualColumn.java: a column computed from an expression over the segment's
+    columns; outputType defaults to FLOAT (:59)."""
+    name: str
+    expression: str
+    outputType: str = "FLOAT"
+
+    def __post_init__(self):
+        if not self.name:
+            raise ValueError("a virtual column needs a name")
+        self.outputType = str(self.outputType or "FLOAT").upper()
+        if self.outputType not in DIMENSION_OUTPUT_TYPES:
+            raise ValueError(f"unknown outputType {self.outputType!r}")
+        self.ast = parse_expression(self.expression)
+
+    def to_json(self):
+        return {"type": "expression", "name": self.name, "expression": self.expression, "outputType": self.outputType}
+
+    @staticmethod
+    def from_json(js) -> "ExpressionVirtualColumn":
+        if isinstance(js, ExpressionVirtualColumn):
+            return js
+        if js.get("type") != "expression":
+            raise ValueError(f"unsupported virtual column type {js.get('type')!r}")
+        return ExpressionVirtualColumn(js["name"], js["expression"], js.get("outputType") or "FLOAT")
+
+
+def parse_virtual_columns(specs) -> List[ExpressionVirtualColumn]:
+    """VirtualColumns.create (segment/VirtualColumns.java:60-90): no duplicate names, no __time; a virtual column
+    that references another one is refused (the engine derives a column from stored columns only)."""
+    out = [ExpressionVirtualColumn.from_json(v) for v in (specs or [])]
+    names = [v.name for v in out]
+    if len(set(names)) != len(names):
+        raise ValueError("duplicate virtual column names")
+    if "__time" in names:
+        raise ValueError("a virtual column cannot be named __time")
+    for v in out:
+        for ident in expression_identifiers(v.ast):
+            if ident in names:
+                raise UnsupportedExpression(f"virtual column {v.name} references virtual column {ident}")
+    return out
+
+
+def _with_virtual_columns(js, query):
+    """virtualColumns only when there are some: a query without them serializes as it always did."""
+    if query.virtualColumns:
+        js["virtualColumns"] = [v.to_json() for v in query.virtualColumns]
+    return js
+
+
+def query_uses_expressions(query) -> bool:
+    """The query needs derived columns: a virtual column, an aggregator expression or an expression filter."""
+    def in_filter(f):
+        if f is None:
+            return False
+        if isinstance(f, ExpressionDimFilter):
+            return True
+        if isinstance(f, (AndDimFilter, OrDimFilter)):
+            return any(in_filter(c) for c in f.fields)
+        return in_filter(f.field) if isinstance(f, NotDimFilter) else False
+    return bool(getattr(query, "virtualColumns", None)) or in_filter(query.filter) or \
+        any(a.expression is not None or in_filter(a.filter) for a in query.aggregations)
+
+
+# ----------------------------------------------------------------------------------------------
 # queries
 # ----------------------------------------------------------------------------------------------
 @dataclass
@@ -1321,10 +1966,12 @@ def _with_post_aggregations(js, query):
 class TimeseriesQuery(BaseQuery):
     descending: bool = False
     postAggregations: List = field(default_factory=list)
+    virtualColumns: List = field(default_factory=list)
 
     def __post_init__(self):
         super().__post_init__()
         self.postAggregations = parse_post_aggregations(self.aggregations, self.postAggregations)
+        self.virtualColumns = parse_virtual_columns(self.virtualColumns)
 
     @property
     def skip_empty_buckets(self) -> bool:
@@ -1333,7 +1980,7 @@ class TimeseriesQuery(BaseQuery):
     def to_json(self):
         js = self._base_json("timeseries")
         js["descending"] = self.descending
-        return _with_post_aggregations(js, self)
+        return _with_virtual_columns(_with_post_aggregations(js, self), self)
 
 
 @dataclass
@@ -1345,9 +1992,14 @@ class TopNQuery(BaseQuery):
     threshold: int = 10
     dimension_type: str = "STRING"
     postAggregations: List = field(default_factory=list)
+    virtualColumns: List = field(default_factory=list)
+    # set by the runners (virtual.lower_query), never serialized: the derived column that stands for a dimension
+    # over a virtual column in the native calls; results keep the dimension's own name
+    derivedDimensions: Dict[str, str] = field(default_factory=dict)
 
     def __post_init__(self):
         super().__post_init__()
+        self.virtualColumns = parse_virtual_columns(self.virtualColumns)
         if isinstance(self.dimension, dict):
             if self.dimension.get("extractionFn") is not None:
                 raise ValueError("extraction functions are out of scope")
@@ -1364,6 +2016,11 @@ class TopNQuery(BaseQuery):
                 self.metric_program()  # (ValueError: no comparator; UnsupportedQuery: no program)
             else:
                 raise ValueError("topN metric must name an aggregator")
+
+    @property
+    def native_dimension(self) -> str:
+        """The column the native calls group by: the dimension, or the derived column that stands for it."""
+        return self.derivedDimensions.get(self.dimension, self.dimension)
 
     def metric_program(self) -> Optional["PostProgram"]:
         """The program of the post-aggregator a numeric / inverted metric spec names (NumericTopNMetricSpec.
@@ -1391,7 +2048,7 @@ class TopNQuery(BaseQuery):
         if self.dimension_type != "STRING":
             dim = {"type": "default", "dimension": dim, "outputName": dim, "outputType": self.dimension_type}
         js.update({"dimension": dim, "metric": self.metric.to_json(), "threshold": self.threshold})
-        return _with_post_aggregations(js, self)
+        return _with_virtual_columns(_with_post_aggregations(js, self), self)
 
 
 @dataclass
@@ -1510,9 +2167,12 @@ class GroupByQuery(BaseQuery):
     having: Optional[HavingSpec] = None
     dimensionTypes: Optional[List[str]] = None
     postAggregations: List = field(default_factory=list)
+    virtualColumns: List = field(default_factory=list)
+    derivedDimensions: Dict[str, str] = field(default_factory=dict)  # (as TopNQuery's)
 
     def __post_init__(self):
         super().__post_init__()
+        self.virtualColumns = parse_virtual_columns(self.virtualColumns)
         if isinstance(self.limitSpec, dict):
             self.limitSpec = DefaultLimitSpec.from_json(self.limitSpec)
         if isinstance(self.having, dict):
@@ -1544,6 +2204,11 @@ class GroupByQuery(BaseQuery):
         self.postAggregations = parse_post_aggregations(self.aggregations, self.postAggregations)
         if any(p.name in dims for p in self.postAggregations):
             raise ValueError("a post-aggregator has the name of a dimension")
+
+    @property
+    def native_dimensions(self) -> List[str]:
+        """The columns the native calls group by (TopNQuery.native_dimension)."""
+        return [self.derivedDimensions.get(d, d) for d in self.dimensions]
 
     def post_aggregator(self, name: str) -> Optional["PostAggregator"]:
         for p in self.postAggregations:
@@ -1616,7 +2281,7 @@ class GroupByQuery(BaseQuery):
             js["limitSpec"] = self.limitSpec.to_json()
         if self.having is not None:
             js["having"] = self.having.to_json()
-        return _with_post_aggregations(js, self)
+        return _with_virtual_columns(_with_post_aggregations(js, self), self)
 
 
 SEARCH_SPEC_TYPES = ("contains", "insensitive_contains", "fragment", "regex", "all")
@@ -1805,15 +2470,20 @@ def query_from_json(js: Dict[str, Any]):
                   granularity=js.get("granularity", "all"), filter=js.get("filter"),
                   aggregations=js.get("aggregations", []), context=js.get("context", {}) or {})
     post = js.get("postAggregations") or []
+    virt = js.get("virtualColumns") or []
     if qt == "timeseries":
-        return TimeseriesQuery(descending=bool(js.get("descending", False)), postAggregations=post, **common)
+        return TimeseriesQuery(descending=bool(js.get("descending", False)), postAggregations=post,
+                               virtualColumns=virt, **common)
     if qt == "topN":
         return TopNQuery(dimension=js["dimension"], metric=js["metric"], threshold=int(js["threshold"]),
-                         postAggregations=post, **common)
+                         postAggregations=post, virtualColumns=virt, **common)
     if qt == "groupBy":
         return GroupByQuery(dimensions=js.get("dimensions", []), limitSpec=js.get("limitSpec"),
                             having=js.get("having"), dimensionTypes=js.get("dimensionTypes"), postAggregations=post,
-                            **common)
+                            virtualColumns=virt, **common)
+    if js.get("virtualColumns"):
+        from ._native import UnsupportedQuery
+        raise UnsupportedQuery(2, f"virtual columns on a {qt} query are out of scope")
     if qt == "search":
         return SearchQuery(searchDimensions=js.get("searchDimensions") or [], query=js.get("query"),
                            sort=js.get("sort") or "lexicographic", limit=int(js.get("limit", 0) or 0), **common)

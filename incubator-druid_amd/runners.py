@@ -43,6 +43,7 @@ import numpy as np
 from . import _native as N
 from . import ordering as O
 from . import query as Q
+from . import virtual as V
 from .segment import GpuSegment
 
 
@@ -138,6 +139,11 @@ class RunStats:
     def __init__(self):
         self.calls: List[Dict] = []
         self.post: List[Dict] = []  # dg_post_info of every groupBy post-processing step on the device
+        # derived columns of the query's expressions (virtual.lower_query): built by this query, found already
+        # built, and the device time of the builds
+        self.derived_built = 0
+        self.derived_reused = 0
+        self.derived_build_ms = 0.0
 
     def add(self, m: N.dg_metrics, span=None):
         d = m.as_dict()
@@ -155,6 +161,7 @@ class RunStats:
 def timeseries_per_segment(segments: Sequence[GpuSegment], query: Q.TimeseriesQuery,
                            stats: Optional[RunStats] = None,
                            cancel: Optional[ctypes.c_int32] = None) -> List[List[Q.Result]]:
+    query = V.lower_query(query, segments, stats, cancel)
     split = segment_queries(query, segments)
     if split is not None:  # every segment on its own calendar chain
         return [timeseries_per_segment([s], q, stats, cancel)[0] if q is not None else []
@@ -192,6 +199,7 @@ def run_timeseries(segments: Sequence[GpuSegment], query: Q.TimeseriesQuery,
     """QueryRunnerFactory.mergeRunners over segments on any devices: one dg_timeseries_run per device,
     then every segment's bucket list (in segment order) folded natively by dg_timeseries_merge
     (TimeseriesBinaryFn, ResultMergeQueryRunner order: time, then runner)."""
+    query = V.lower_query(query, segments, stats)
     na = _native_width(query)
     groups = list(_group_by_device(segments).items())
     caps = {dev: _bucket_cap([segments[i] for i in idx], query) for dev, idx in groups}
@@ -522,7 +530,7 @@ def _numeric_dimension(segments: Sequence[GpuSegment], query: Q.TopNQuery) -> bo
     """The topN runs over a numeric dimension: a numeric output type, or a LONG / FLOAT / DOUBLE column."""
     if query.dimension_type != "STRING":
         return True
-    dim = query.dimension
+    dim = query.native_dimension
     for s in segments:
         if s.column_type(dim) in _NUMERIC_COLS:
             return True
@@ -539,7 +547,7 @@ def _topn_opts(query: Q.TopNQuery, cut_ties: Optional[np.ndarray] = None) -> N.d
 def topn_dim_values(seg: GpuSegment, query: Q.TopNQuery, ids) -> List:
     """The dimension values of result ids: dictionary strings, or for a numeric column the values converted
     to the dimension's output type (convertAggregatorStoreKeyToColumnValue): int, float, or the decimal str."""
-    dim = query.dimension
+    dim = query.native_dimension
     if seg.column_type(dim) not in _NUMERIC_COLS:
         return [seg.dim_value(dim, int(x)) for x in ids]
     vals = seg.numeric_dim_values(dim, ids).tolist()
@@ -551,7 +559,7 @@ def _topn_struct(query: Q.TopNQuery, threshold: int, segments: Optional[Sequence
     dictionary orders are registered and their previousStop cuts computed). Returns the struct and
     the buffers it points into."""
     t = N.dg_topn()
-    dim = query.dimension.encode()
+    dim = query.native_dimension.encode()
     t.dimension = dim
     t.threshold = threshold
     spec = query.metric
@@ -607,6 +615,7 @@ def topn_raw(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
     _check_topn(query)
     if len(_group_by_device(segments)) != 1:
         raise ValueError("topn_raw: segments must share one device")
+    query = V.lower_query(query, segments, stats, cancel)
     na = _native_width(query)
     K = query.segment_threshold
     scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
@@ -762,6 +771,7 @@ def run_topn(segments: Sequence[GpuSegment], query: Q.TopNQuery, stats: Optional
     """Per-segment topN on the GPU + TopNBinaryFn merge in the engine (one device); falls back to the
     Python merge when the segments span devices."""
     _check_topn(query)
+    query = V.lower_query(query, segments, stats)
     if len(_group_by_device(segments)) != 1 or not query.granularity.is_all:
         return merge_topn(query, topn_per_segment(segments, query, stats))
     if query.metric.type == "dimension":
@@ -784,6 +794,7 @@ def topn_per_segment(segments: Sequence[GpuSegment], query: Q.TopNQuery,
     """Per-segment results (what each segment's QueryRunner returns), as Result lists.
     descending: topn_raw's descending cursors."""
     _check_topn(query)
+    query = V.lower_query(query, segments, stats)
     split = segment_queries(query, segments)
     if split is not None:  # every segment on its own calendar chain
         return [topn_per_segment([s], q, stats, descending)[0] if q is not None else []
@@ -1178,9 +1189,10 @@ def groupby_run(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     the query context's "timeout" (ms) fails it with DG_ERR_TIMEOUT."""
     if len(_group_by_device(segments)) != 1:
         raise ValueError("groupby_run: segments must share one device")
+    query = V.lower_query(query, segments, stats, cancel)
     nd = len(query.dimensions)
     scan, keep = N.make_scan(query, Q, segments=segments, cancel=cancel)
-    dims = (ctypes.c_char_p * max(nd, 1))(*[d.encode() for d in query.dimensions])
+    dims = (ctypes.c_char_p * max(nd, 1))(*[d.encode() for d in query.native_dimensions])
     g = N.dg_groupby()
     g.dimensions = ctypes.cast(dims, ctypes.POINTER(ctypes.c_char_p))
     g.n_dims = nd
@@ -1221,6 +1233,7 @@ def groupby_per_device(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     post_process: the caller merges nothing else into these groups (the merged runner over one device's
     segments), so the having and limit specs run on the device before the fetch; per-segment partials
     and several devices' partials are merged first and stay whole."""
+    query = V.lower_query(query, segments, stats)
     out = []
     groups = _group_by_device(segments)
     for _, idx in groups.items():
@@ -1273,6 +1286,7 @@ def groupby_merge_devices(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
     for a in query.aggregations:  # (before any engine call or peer copy)
         if a.is_pair:
             raise N.UnsupportedQuery(2, f"{a.type}({a.name}): the device-side groupBy merge does not combine first/last pairs")
+    query = V.lower_query(query, segments, stats)  # (before the devices' threads start)
     groups = _group_by_device(segments)
     parts = []
     try:
@@ -1297,6 +1311,7 @@ def groupby_per_segment(segments: Sequence[GpuSegment], query: Q.GroupByQuery,
                         stats: Optional[RunStats] = None) -> List[GroupByPartial]:
     """What each segment's QueryRunner returns (createRunner(segment).run), one engine call each
     (a calendar granularity on the segment's own bucket chain, segment_queries)."""
+    query = V.lower_query(query, segments, stats)
     split = segment_queries(query, segments) or [query] * len(segments)
     return [groupby_per_device([s], q, stats)[0] for s, q in zip(segments, split) if q is not None]
 
@@ -2226,7 +2241,7 @@ class SegmentQueryRunner:
         self.factory, self.segment = factory, segment
 
     def run(self, query):
-        query = exact_granularity(query, [self.segment])
+        query = exact_granularity(V.lower_query(query, [self.segment]), [self.segment])
         split = segment_queries(query, [self.segment])
         if split is not None:
             return _run_split(self.factory, [self.segment], split, query, None)
@@ -2242,7 +2257,7 @@ class MergedQueryRunner:
         self.stats = RunStats()
 
     def run(self, query):
-        query = exact_granularity(query, self.segments)
+        query = exact_granularity(V.lower_query(query, self.segments, self.stats), self.segments)
         split = segment_queries(query, self.segments)
         if split is not None:
             return _run_split(self.factory, self.segments, split, query, self.stats)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -81,6 +82,8 @@ class GpuSegment:
         self._orders: Dict[Tuple[str, int], O.DictionaryOrder] = {}
         self._types: Dict[str, int] = {}  # a segment's columns never change once attached / built
         self._values: Dict[str, Dict[int, Optional[str]]] = {}  # dim_value lookups already made
+        self._derived: "OrderedDict[str, int]" = OrderedDict()  # derived column -> its HBM bytes, LRU first
+        self._derive_lock = threading.RLock()  # (derive / drop_derived: the LRU and the engine stay in step)
 
     # -- StorageAdapter-ish facts ------------------------------------------------------------
     def columns(self) -> List[str]:
@@ -188,6 +191,54 @@ class GpuSegment:
         if len(seen) < 65536:  # the ids a query's results name again (topN heads), bounded
             seen[int(idx)] = v
         return v
+
+    # -- derived columns (dg_segment_derive_column) ------------------------------------------------
+    MAX_DERIVED = 8  # derived columns kept per segment: each holds 8 B (FLOAT: 4 B) per row of HBM
+
+    def derive(self, name: str, ops, inputs, out_type: int, in_use=(), cancel=None, timeout_ms: int = 0) -> Dict:
+        """The derived column `name` = the expression program over this segment's rows, built on the device unless
+        an identical one is there. At most MAX_DERIVED are kept: beyond that the least recently used one that is
+        not among `in_use` (the running query's) is dropped first. Returns dg_derived_info as a dict
+        (built = 0: reused). UnsupportedQuery: a string or missing input, a division by zero in some row.
+        One querying thread at a time: `in_use` protects the running query's columns against this call's own
+        evictions only. A second thread that derives on the same segment while the first one's engine call has
+        not run yet may evict a column the first query names, which the engine would read as a missing column;
+        the lock below keeps the bookkeeping whole, it does not pin columns across calls. Callers that share a
+        segment between threads serialise their queries on it."""
+        with self._derive_lock:
+            return self._derive(name, ops, inputs, out_type, in_use, cancel, timeout_ms)
+
+    def _derive(self, name, ops, inputs, out_type, in_use, cancel, timeout_ms) -> Dict:
+        held = self._derived
+        if name in held:
+            held.move_to_end(name)
+            return {"built": 0, "type": out_type, "rows": self.num_rows, "device_bytes": held[name],
+                    "poisoned_rows": 0, "build_ms": 0.0}
+        while len(held) >= self.MAX_DERIVED:
+            victim = next((n for n in held if n not in in_use), None)
+            if victim is None:
+                raise N.UnsupportedQuery(2, f"a query needs more than {self.MAX_DERIVED} derived columns of a segment")
+            self.drop_derived(victim)
+        e, keep = N.make_expr(ops, inputs, out_type)
+        info = N.dg_derived_info()
+        N.check(N.lib().dg_segment_derive_column(self.handle, name.encode(), ctypes.byref(e),
+                                                 ctypes.pointer(cancel) if cancel is not None else None,
+                                                 int(timeout_ms), ctypes.byref(info)))
+        held[name] = info.device_bytes
+        self._types[name] = out_type
+        return info.as_dict()
+
+    def derived_columns(self) -> List[str]:
+        """The derived columns held, least recently used first."""
+        return list(self._derived)
+
+    def drop_derived(self, name: Optional[str] = None) -> None:
+        """Drop one derived column (dg_segment_drop_derived), or all of them: their HBM goes back."""
+        with self._derive_lock:
+            for n in ([name] if name is not None else list(self._derived)):
+                N.check(N.lib().dg_segment_drop_derived(self.handle, n.encode()))
+                del self._derived[n]
+                self._types.pop(n, None)
 
     def filter_bitmap(self, flt, query_module) -> Tuple[np.ndarray, int]:
         """Filter.getBitmapResult as a dense row bitset (uint32 words) + cardinality."""
